@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """PairHMM throughput bench (GCUPS) for the MI355X engine.
 
-    python bench.py [--gpus N --steps K --warmup W --workload S2]
+    python bench.py [--gpus N --steps K --warmup W --workload S2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up the batch, warms up, times the K steps and prints the
+result line (with --dump-outputs DIR it also writes the last timed step's
+results there). --full adds everything else this file measures and checks:
+the end-to-end call path, the CPU baselines and their parity checks, the
+secondary configs (S1, S1w, S4, shards, region calls, Smith-Waterman, the
+genotyper) and the detail file; --no-cpu and --no-extra trim a --full run.
 
 Workload (BASELINE.json configs[2] / configs[3]): the seeded synthetic WGS-mix
 batch S2 — 1 000 000 independent (read, hap) pairs, H ~ U[100, 500],
@@ -499,6 +506,28 @@ def compact_line(out, detail_path):
     return line
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each per-pair result array as path/<name>.npy, float32 or
+    float64 (the rescue flags as float32 0/1). A batch whose arrays pass
+    DUMP_MAX_BYTES in all is written as a fixed, seeded sample of its pairs,
+    with the sampled pair indices beside it (index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, v.dtype if v.dtype in (np.float32, np.float64) else np.float32)
+              for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_pair = sum(v.itemsize for v in arrays.values())
+    if n * per_pair > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (per_pair + 8)
+        idx = np.sort(np.random.default_rng(20).choice(n, keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -510,8 +539,14 @@ def main():
                     help="run rank 0's shard of an N-way split of the batch (shard.shard_pairs), at one GPU")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core of this process's CPU set")
     ap.add_argument("--cpu-reps", type=int, default=2)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip end-to-end and secondary configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the end-to-end call path, the CPU baselines and parity checks and the "
+                         "secondary configs, and write the detail file (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (raw_f32, raw_f64, rescued; batch order) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip end-to-end and secondary configs")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo only to rehearse N ranks on one GPU")
     ap.add_argument("--check", type=int, default=0,
@@ -521,6 +556,8 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="use the process group / gather path even at WORLD_SIZE=1 (tests of the RCCL path)")
     args = ap.parse_args()
+    extra = args.full and not args.no_extra   # end-to-end and secondary configs
+    cpu = args.full and not args.no_cpu       # CPU baselines and parity against them
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -630,6 +667,20 @@ def main():
     ms_step = elapsed / args.steps * 1e3
     value = total_cells * args.steps / elapsed / 1e9
 
+    if args.dump_outputs and rank == 0:
+        # What the last timed step handed its caller: the bound output set of
+        # that step (one rank) or rank 0's gather buffers (every rank's shard),
+        # put back in batch order.
+        last = outs[(nstep[0] - 1) % nsets]
+        if distributed:
+            got = {"raw_f32": np.zeros(n_total, np.float32), "raw_f64": np.zeros(n_total, np.float64)}
+            for r, sh in enumerate(shards):
+                got["raw_f32"][sh] = g32[r][: len(sh)].cpu().numpy()
+                got["raw_f64"][sh] = g64[r][: len(sh)].cpu().numpy()
+        else:
+            got = {k: t[:n_total].cpu().numpy() for k, t in zip(("raw_f32", "raw_f64", "rescued"), last)}
+        dump_outputs(args.dump_outputs, got)
+
     # Dominant kernel: the fp32 PairHMM pass. Algorithmic work 12 ops/cell.
     k_ms = st.kernel_ms_f32
     achieved = FLOPS_PER_CELL * my_cells / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
@@ -674,11 +725,11 @@ def main():
 
     # The real call path, timed before the CPU baseline's all-core run (which
     # leaves the host's caches and clocks in another state for a while).
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and extra:
         out.update(end_to_end(hcphmm, W, batch, total_cells))
 
     cpu_res = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and cpu:
         cores, model = host_cpu()
         thr = args.cpu_threads or cores
         cb, cpu_res = cpu_baseline(batch, thr, args.cpu_reps,
@@ -686,13 +737,13 @@ def main():
                                    f"(every CPU of this process's share), best of {args.cpu_reps}")
         cb.update(nproc=cores, cpu_model=model, machine_cpus=os.cpu_count())
         out["cpu_baseline"] = cb
-        if not args.no_extra:
+        if extra:
             s1 = W.subset(batch, np.arange(min(n_total, 20_000)))
             c1, _ = cpu_baseline(s1, 1, 1, f"first {len(s1['R'])} pairs of {args.workload}, 1 thread "
                                            "(the reference as built: OpenMP compiled out)")
             out["cpu_baseline_1core"] = c1
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         r = bt.results()
         out["config"]["rescued_fp64"] = int(r["rescued"].sum())
         m = r["rescued"].astype(bool)
@@ -702,7 +753,7 @@ def main():
                                       np.ascontiguousarray(cpu_res[k]).view(np.uint8))
                        for k in ("raw_f32", "rescued", "loglik"))
             out["parity_vs_cpu_reference"] = "bit-exact" if same else "MISMATCH"
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and extra:
         sec = {}
         # S1w1M: the north star's 101x250 shape at a size that fills the chip
         # (S1/S1w are 10k-pair, latency-bound passes of < 0.15 ms).
@@ -726,9 +777,9 @@ def main():
             sec[label]["implied_efficiency_vs_1gpu_cold"] = round(
                 out["device_pass_ms"] / (nr * sec[label]["device_pass_ms_cold"]), 4) \
                 if sec[label]["device_pass_ms_cold"] else None
-        sec.update(region_calls(hcphmm, W, args.no_cpu))
-        sec["smith_waterman"] = sw_secondary(args.no_cpu)
-        sec["genotyper"] = gt_secondary(args.no_cpu)
+        sec.update(region_calls(hcphmm, W, not cpu))
+        sec["smith_waterman"] = sw_secondary(not cpu)
+        sec["genotyper"] = gt_secondary(not cpu)
         out["secondary"] = sec
     if distributed:
         out["gather"] = (f"dist.gather ({'gloo, rehearsal' if gloo else 'RCCL'}) of raw_f32 + raw_f64 per step"
@@ -768,10 +819,13 @@ def main():
         # to a file; stdout carries one compact line (< 2 kB) that a driver's
         # output tail holds whole (verdict round 5, item 5).
         detail = os.environ.get("HC_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
+        if not args.full:   # a plain run prints its line and writes no detail file
+            detail = None
         try:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(out, f, indent=1)
+            if detail:
+                os.makedirs(os.path.dirname(detail), exist_ok=True)
+                with open(detail, "w") as f:
+                    json.dump(out, f, indent=1)
         except OSError:
             detail = None
         print(json.dumps(compact_line(out, detail), separators=(",", ":")), flush=True)

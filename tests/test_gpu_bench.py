@@ -27,6 +27,38 @@ def _free_port():
         return sk.getsockname()[1]
 
 
+def test_plain_run_dumps_the_timed_steps_outputs(tmp_path, oracle_lib):
+    """A plain run (no --full) times exactly --steps steps, prints the contract's
+    fields and none of the --full extras, and --dump-outputs writes the last
+    timed step's per-pair results: float arrays in batch order, bit-identical
+    to the oracle on the same seeded batch."""
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--pairs", "3001", "--dump-outputs", str(dump)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["config"]["pairs"] == 3001
+    assert out["unit"] == "GCUPS" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["ms_per_step"] > 0
+    # value and ms_per_step are the same measurement; the line rounds ms_per_step
+    # to 0.001 ms, at most 0.0005 / 0.02 = 2.5 % of a step of this size (> 0.02 ms)
+    assert out["value"] == pytest.approx(out["config"]["cells"] / (out["ms_per_step"] * 1e-3) / 1e9, rel=0.03)
+    for k in ("cpu_baseline", "parity_vs_cpu_reference", "end_to_end_gcups", "secondary"):
+        assert k not in out, k
+    assert out["detail"] is None
+    got = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert sorted(got) == ["raw_f32", "raw_f64", "rescued"]
+    assert got["raw_f32"].dtype == np.float32 and got["raw_f64"].dtype == np.float64
+    assert got["rescued"].dtype == np.float32
+    ref = oracle_lib.pairs(W.config("S2", 3001), nthreads=4)
+    assert np.array_equal(got["raw_f32"].view(np.uint32), ref["raw_f32"].view(np.uint32))
+    assert np.array_equal(got["rescued"], ref["rescued"].astype(np.float32))
+    m = ref["rescued"].astype(bool)
+    assert np.array_equal(got["raw_f64"][m].view(np.uint64), ref["raw_f64"][m].view(np.uint64))
+    assert (got["raw_f64"][~m] == 0).all()
+
+
 def test_two_rank_gloo_check_is_bit_exact(tmp_path, oracle_lib):
     npz = tmp_path / "gathered.npz"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",

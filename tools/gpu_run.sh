@@ -9,8 +9,8 @@
 #   tests                     the whole -m gpu suite
 #   tests:EXPR                the -m gpu tests matching pytest -k EXPR
 #   smoke                     __graft_entry__.smoke()
-#   bench                     bench.py with its defaults (the BENCH line)
-#   bench:ARGS                bench.py ARGS (commas for spaces), e.g. bench:--workload,S4,--no-cpu,--no-extra
+#   bench                     bench.py --full with its defaults (the BENCH line with every secondary)
+#   bench:ARGS                bench.py --full ARGS (commas for spaces), e.g. bench:--workload,S4,--no-cpu,--no-extra
 #   profile:CFG               tools/profile_cfg.sh CFG (commas for spaces), e.g. profile:S4,20000
 #   profiles                  every bench config's profile (S2 S1 S4 S4_20000 both shards, the region)
 #   ab:WL:PAIRS:VARIANTS      tools/persist_ab.sh with NO_R3=1; PAIRS comma-separated, VARIANTS
@@ -41,7 +41,7 @@ for step in "$@"; do
       rc=$?; tail -2 $OUT/smoke.log ;;
     bench)
       n=$(ls $OUT | grep -c '^bench')
-      HC_BENCH_DETAIL=$PWD/$OUT/bench_${n}_detail.json timeout -k 10 600 python3 bench.py ${arg//,/ } \
+      HC_BENCH_DETAIL=$PWD/$OUT/bench_${n}_detail.json timeout -k 10 600 python3 bench.py --full ${arg//,/ } \
           > $OUT/bench_$n.json 2> $OUT/bench_$n.err
       rc=$?
       [ $rc -eq 0 ] && python3 tools/bench_brief.py $OUT/bench_${n}_detail.json && wc -c $OUT/bench_$n.json ;;

@@ -14,7 +14,7 @@ WL=$1; NP=$2; W=5; ROUND=${ROUND:-r05}
 NAME=$WL${NP:+_$NP}
 ARGS="--workload $WL ${NP:+--pairs $NP} --steps 20 --warmup $W"
 if [ "$WL" = S2shard ]; then ARGS="--workload S2 --shard-of $NP --steps 20 --warmup $W"; fi
-B="python3 bench.py $ARGS --no-cpu --no-extra"
+B="python3 bench.py $ARGS --full --no-cpu --no-extra"   # --full: the detail record (cells, rescued cells) read below
 EXTRA=""
 if [ "$WL" = region ]; then
     NAME=region_415x$NP
