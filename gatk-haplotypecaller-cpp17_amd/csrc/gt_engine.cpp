@@ -18,6 +18,7 @@
 #include "../../include/hc_gt.h"
 #include "../../include/hc_pairhmm.h"
 #include "gt_kernels.hpp"
+#include "gt_plan_kernels.hpp"
 #include "pool.hpp"
 
 // MathUtils Jacobian table as g++ folds it at compile time (tools/gen_jacobian.py).
@@ -89,6 +90,17 @@ int reserve(size_t dev, size_t host)
 }
 
 size_t up(size_t x) { return (x + 255) & ~size_t(255); }
+
+// The one launch of the arithmetic, shared by hc_gt_genotype_sites (records,
+// keep lists and maps uploaded) and hc_gt_call_regions (written on the device).
+hipError_t launch_arithmetic(GtArgs& a)
+{
+    a.jac = g_jac;
+    const double table_step = 0.0001;   // JacobianLogTable::TABLE_STEP (math_utils.hpp:24)
+    a.inv_step = 1.0 / table_step;      // INV_STEP (:25)
+    a.log10_2 = std::log10(2.0);        // std::log10(2) (genotyper.hpp:280,321)
+    return launch_sites(a, g_stream);
+}
 
 int run(const hc_gt_site* sites, int32_t n)
 {
@@ -183,15 +195,11 @@ int run(const hc_gt_site* sites, int32_t n)
     a.L = reinterpret_cast<const double*>(g_dev + o_L);
     a.keep = reinterpret_cast<const int32_t*>(g_dev + o_keep);
     a.amap = reinterpret_cast<const int32_t*>(g_dev + o_map);
-    a.jac = g_jac;
-    const double table_step = 0.0001;   // JacobianLogTable::TABLE_STEP (math_utils.hpp:24)
-    a.inv_step = 1.0 / table_step;      // INV_STEP (:25)
-    a.log10_2 = std::log10(2.0);        // std::log10(2) (genotyper.hpp:280,321)
     a.al = reinterpret_cast<double*>(g_dev + o_al);
     a.gl = reinterpret_cast<double*>(g_dev + o_gl);
     a.gi = reinterpret_cast<int32_t*>(g_dev + o_gi);
     a.gq = reinterpret_cast<int32_t*>(g_dev + o_gq);
-    HIP_TRY(launch_sites(a, g_stream));
+    HIP_TRY(launch_arithmetic(a));
     HIP_TRY(hipMemcpyAsync(h, g_dev + o_gl, tail, hipMemcpyDeviceToHost, g_stream));
     HIP_TRY(hipStreamSynchronize(g_stream));
     const double* gl = reinterpret_cast<const double*>(h);
@@ -207,7 +215,318 @@ int run(const hc_gt_site* sites, int32_t n)
     return HC_PHMM_OK;
 }
 
+
+// ---- hc_gt_call_regions: events, sites, alleles, maps and kept reads on the device ----
+
+struct Calls {
+    std::vector<hc_gt_call_site> sites;
+    std::vector<char> text;          // allele strings, NUL-terminated
+    std::vector<const char*> ptrs;   // per site, n_alleles pointers into text
+    std::vector<int32_t> ints;       // the downloaded keep and hap_allele blocks
+    std::vector<double> gl;
+};
+
+// "%d%c" runs of M I D S, each with the window and haplotype position it starts at.
+bool parse_cigar(const char* t, int32_t begin, std::vector<PlanRun>& runs, int32_t& ref_pos, int32_t& hap_pos)
+{
+    ref_pos = begin;
+    hap_pos = 0;
+    if (!*t) return false;
+    while (*t) {
+        if (*t < '0' || *t > '9') return false;
+        int64_t len = 0;
+        while (*t >= '0' && *t <= '9') {
+            len = len * 10 + (*t++ - '0');
+            if (len > HC_GT_MAX_REF_LEN + HC_GT_MAX_HAP_LEN) return false;
+        }
+        if (len < 1) return false;
+        PlanRun r{int32_t(len), 0, ref_pos, hap_pos};
+        switch (*t++) {
+        case 'M': r.op = kOpM; ref_pos += r.len; hap_pos += r.len; break;
+        case 'I': r.op = kOpI; hap_pos += r.len; break;
+        case 'D': r.op = kOpD; ref_pos += r.len; break;
+        case 'S': r.op = kOpS; hap_pos += r.len; break;
+        default: return false;   // the reference throws on any other operator
+        }
+        if (ref_pos > HC_GT_MAX_REF_LEN || hap_pos > HC_GT_MAX_HAP_LEN) return false;
+        runs.push_back(r);
+    }
+    return true;
+}
+
+char* g_dev2 = nullptr;   // buffers sized by the site count
+size_t g_dev2_bytes = 0;
+
+int reserve_sites(size_t dev)
+{
+    if (dev <= g_dev2_bytes) return HC_PHMM_OK;
+    if (g_dev2) (void)hipFree(g_dev2);
+    g_dev2 = nullptr;
+    g_dev2_bytes = 0;
+    if (hipMalloc(&g_dev2, dev + dev / 4) != hipSuccess) return fail(HC_PHMM_ENOMEM, "genotyper site workspace");
+    g_dev2_bytes = dev + dev / 4;
+    return HC_PHMM_OK;
+}
+
+int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
+{
+    std::vector<PlanRegion> pr(static_cast<size_t>(n));
+    std::vector<PlanHap> ph;
+    std::vector<PlanRun> runs;
+    std::string hap_pool;
+    int64_t ref_total = 0, read_total = 0, L_total = 0, tab_total = 0, keep_bound = 0, map_bound = 0, site_bound = 0;
+    for (int32_t r = 0; r < n; ++r) {
+        const hc_gt_region& x = regions[r];
+        const std::string at = "region " + std::to_string(r);
+        if (!x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.L)))
+            return fail(HC_PHMM_EINVAL, at + ": null pointer");
+        if (x.ref_len < 1 || x.ref_len > HC_GT_MAX_REF_LEN || x.n_haps < 1 || x.n_haps > HC_GT_MAX_HAPS || x.n_reads < 0)
+            return fail(HC_PHMM_EINVAL, at + ": ref_len, n_haps or n_reads out of range");
+        if (x.padded_begin < 0 || x.origin_begin < x.padded_begin || x.origin_end < x.origin_begin ||
+            x.origin_end > x.padded_begin + x.ref_len)
+            return fail(HC_PHMM_EINVAL, at + ": origin outside the padded window");
+        PlanRegion& d = pr[size_t(r)];
+        d.padded_begin = x.padded_begin;
+        d.origin_begin = x.origin_begin;
+        d.origin_end = x.origin_end;
+        d.L_off = L_total;
+        d.ref_off = int32_t(ref_total);
+        d.ref_len = x.ref_len;
+        d.hap0 = int32_t(ph.size());
+        d.n_haps = x.n_haps;
+        d.read_off = int32_t(read_total);
+        d.n_reads = x.n_reads;
+        for (int32_t h = 0; h < x.n_haps; ++h) {
+            const hc_gt_hap_aln& y = x.haps[h];
+            const std::string hat = at + " haplotype " + std::to_string(h);
+            if (!y.bases || !y.cigar) return fail(HC_PHMM_EINVAL, hat + ": null pointer");
+            if (y.length < 1 || y.length > HC_GT_MAX_HAP_LEN || y.alignment_begin < 0 || y.alignment_begin > x.ref_len)
+                return fail(HC_PHMM_EINVAL, hat + ": length or alignment_begin out of range");
+            PlanHap e;
+            e.region = r;
+            e.base_off = int32_t(hap_pool.size());
+            e.run_off = int32_t(runs.size());
+            e.tab_off = int32_t(tab_total);
+            int32_t ref_end = 0, hap_end = 0;
+            if (!parse_cigar(y.cigar, y.alignment_begin, runs, ref_end, hap_end))
+                return fail(HC_PHMM_EINVAL, hat + ": bad CIGAR '" + std::string(y.cigar).substr(0, 64) + "'");
+            if (hap_end != y.length)
+                return fail(HC_PHMM_EINVAL, hat + ": CIGAR consumes " + std::to_string(hap_end) + " bases of " +
+                                                std::to_string(y.length));
+            if (ref_end > x.ref_len) return fail(HC_PHMM_EINVAL, hat + ": CIGAR runs past the reference window");
+            e.n_runs = int32_t(runs.size()) - e.run_off;
+            hap_pool.append(reinterpret_cast<const char*>(y.bases), size_t(y.length));
+            ph.push_back(e);
+            tab_total += x.ref_len;
+        }
+        const int64_t width = std::min<int64_t>(x.origin_end - x.origin_begin, x.ref_len);
+        ref_total += x.ref_len;
+        read_total += x.n_reads;
+        L_total += int64_t(x.n_reads) * x.n_haps;
+        site_bound += width;
+        keep_bound += width * x.n_reads;
+        map_bound += width * x.n_haps;
+        if (tab_total > INT32_MAX || hap_pool.size() > size_t(INT32_MAX) || runs.size() > size_t(INT32_MAX) ||
+            read_total > INT32_MAX || site_bound * kMaxGenotypes > INT32_MAX || keep_bound > INT32_MAX ||
+            map_bound > INT32_MAX)
+            return fail(HC_PHMM_EINVAL, "too many regions for one call");
+    }
+    // Workspace 1: [regions | haps | runs | ref | hap | read_begin | read_end | L] uploaded, then
+    // [bitmap | base | totals | ev | span] written by the events and scan kernels.
+    const size_t nh = ph.size();
+    const size_t o_reg = 0;
+    const size_t o_hap = up(o_reg + sizeof(PlanRegion) * size_t(n));
+    const size_t o_run = up(o_hap + sizeof(PlanHap) * nh);
+    const size_t o_ref = up(o_run + sizeof(PlanRun) * runs.size());
+    const size_t o_pool = up(o_ref + size_t(ref_total));
+    const size_t o_rb = up(o_pool + hap_pool.size());
+    const size_t o_re = up(o_rb + sizeof(int64_t) * size_t(read_total));
+    const size_t o_L = up(o_re + sizeof(int64_t) * size_t(read_total));
+    const size_t in_bytes = up(o_L + sizeof(double) * size_t(L_total));
+    const size_t o_bm = in_bytes;
+    const size_t o_base = up(o_bm + sizeof(uint32_t) * kBitmapWords * size_t(n));
+    const size_t o_tot = up(o_base + sizeof(PlanBase) * size_t(n));
+    const size_t o_ev = up(o_tot + sizeof(PlanTotals));
+    const size_t o_span = up(o_ev + sizeof(int16_t) * size_t(tab_total));
+    const size_t dev_bytes = up(o_span + sizeof(int16_t) * size_t(tab_total));
+    const size_t h_tot = in_bytes;   // the totals land behind the staged input
+    int rc = reserve(dev_bytes, in_bytes + 256);
+    if (rc) return rc;
+    char* h = g_host;
+    std::memcpy(h + o_reg, pr.data(), sizeof(PlanRegion) * size_t(n));
+    std::memcpy(h + o_hap, ph.data(), sizeof(PlanHap) * nh);
+    std::memcpy(h + o_run, runs.data(), sizeof(PlanRun) * runs.size());
+    std::memcpy(h + o_pool, hap_pool.data(), hap_pool.size());
+    for (int32_t r = 0; r < n; ++r) {
+        const hc_gt_region& x = regions[r];
+        std::memcpy(h + o_ref + size_t(pr[size_t(r)].ref_off), x.ref, size_t(x.ref_len));
+        if (x.n_reads) {
+            std::memcpy(h + o_rb + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_begin, sizeof(int64_t) * size_t(x.n_reads));
+            std::memcpy(h + o_re + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_end, sizeof(int64_t) * size_t(x.n_reads));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(g_dev, h, o_L, hipMemcpyHostToDevice, g_stream));
+    PlanArgs p{};
+    p.regions = reinterpret_cast<const PlanRegion*>(g_dev + o_reg);
+    p.n_regions = n;
+    p.haps = reinterpret_cast<const PlanHap*>(g_dev + o_hap);
+    p.n_haps = int(nh);
+    p.runs = reinterpret_cast<const PlanRun*>(g_dev + o_run);
+    p.ref = reinterpret_cast<const uint8_t*>(g_dev + o_ref);
+    p.hap = reinterpret_cast<const uint8_t*>(g_dev + o_pool);
+    p.read_begin = reinterpret_cast<const int64_t*>(g_dev + o_rb);
+    p.read_end = reinterpret_cast<const int64_t*>(g_dev + o_re);
+    p.ev = reinterpret_cast<int16_t*>(g_dev + o_ev);
+    p.span = reinterpret_cast<int16_t*>(g_dev + o_span);
+    p.bitmap = reinterpret_cast<uint32_t*>(g_dev + o_bm);
+    p.base = reinterpret_cast<PlanBase*>(g_dev + o_base);
+    p.totals = reinterpret_cast<PlanTotals*>(g_dev + o_tot);
+    HIP_TRY(launch_plan_events(p, g_stream));
+    HIP_TRY(hipMemcpyAsync(h + h_tot, g_dev + o_tot, sizeof(PlanTotals), hipMemcpyDeviceToHost, g_stream));
+    // The matrices are staged while the events and scan kernels run.
+    hcphmm::parallel_for(n, [&](int64_t lo, int64_t hi) {
+        for (int64_t r = lo; r < hi; ++r) {
+            const hc_gt_region& x = regions[r];
+            if (x.n_reads)
+                std::memcpy(h + o_L + sizeof(double) * size_t(pr[size_t(r)].L_off), x.L,
+                            sizeof(double) * size_t(x.n_reads) * size_t(x.n_haps));
+        }
+    }, 1);
+    if (in_bytes > o_L) HIP_TRY(hipMemcpyAsync(g_dev + o_L, h + o_L, in_bytes - o_L, hipMemcpyHostToDevice, g_stream));
+    // The one counted readback: the site count sizes everything that follows.
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    PlanTotals tot;
+    std::memcpy(&tot, h + h_tot, sizeof(tot));
+    const int64_t ns = tot.n_sites;
+    if (ns < 0 || ns > site_bound || tot.keep_cap > keep_bound || tot.map_cap > map_bound)
+        return fail(HC_PHMM_EHIP, "genotyper site count out of its bound");
+    if (ns == 0) return HC_PHMM_OK;
+    // Workspace 2: [site_out | gl | gi | gq | keep | amap] read back, then [gt_sites | al] scratch.
+    const size_t o_so = 0;
+    const size_t o_gl = up(o_so + sizeof(SiteOut) * size_t(ns));
+    const size_t o_gi = up(o_gl + sizeof(double) * kMaxGenotypes * size_t(ns));
+    const size_t o_gq = up(o_gi + sizeof(int32_t) * size_t(ns));
+    const size_t o_keep = up(o_gq + sizeof(int32_t) * size_t(ns));
+    const size_t o_map = o_keep + sizeof(int32_t) * size_t(tot.keep_cap);
+    const size_t back = up(o_map + sizeof(int32_t) * size_t(tot.map_cap));
+    const size_t o_gs = back;
+    const size_t o_al = up(o_gs + sizeof(GtSite) * size_t(ns));
+    const size_t dev2_bytes = up(o_al + sizeof(double) * kMaxAlleles * size_t(std::max<int64_t>(tot.keep_cap, 1)));
+    rc = reserve_sites(dev2_bytes);
+    if (rc) return rc;
+    rc = reserve(0, back);
+    if (rc) return rc;
+    h = g_host;
+    p.site_out = reinterpret_cast<SiteOut*>(g_dev2 + o_so);
+    p.gt_sites = reinterpret_cast<GtSite*>(g_dev2 + o_gs);
+    p.keep = reinterpret_cast<int32_t*>(g_dev2 + o_keep);
+    p.amap = reinterpret_cast<int32_t*>(g_dev2 + o_map);
+    HIP_TRY(launch_plan_sites(p, ns, g_stream));
+    GtArgs a{};
+    a.sites = p.gt_sites;
+    a.n = int(ns);
+    a.L = reinterpret_cast<const double*>(g_dev + o_L);
+    a.keep = p.keep;
+    a.amap = p.amap;
+    a.al = reinterpret_cast<double*>(g_dev2 + o_al);
+    a.gl = reinterpret_cast<double*>(g_dev2 + o_gl);
+    a.gi = reinterpret_cast<int32_t*>(g_dev2 + o_gi);
+    a.gq = reinterpret_cast<int32_t*>(g_dev2 + o_gq);
+    HIP_TRY(launch_arithmetic(a));
+    HIP_TRY(hipMemcpyAsync(h, g_dev2, back, hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    // Materialise the records: strings from the alt descriptors, pointers into the copied blocks.
+    const SiteOut* so = reinterpret_cast<const SiteOut*>(h + o_so);
+    const double* gl = reinterpret_cast<const double*>(h + o_gl);
+    const int32_t* gi = reinterpret_cast<const int32_t*>(h + o_gi);
+    const int32_t* gq = reinterpret_cast<const int32_t*>(h + o_gq);
+    out.ints.resize(size_t(tot.keep_cap + tot.map_cap));
+    std::memcpy(out.ints.data(), h + o_keep, sizeof(int32_t) * out.ints.size());
+    const int32_t* keep = out.ints.data();
+    const int32_t* amap = out.ints.data() + tot.keep_cap;
+    out.sites.resize(size_t(ns));
+    size_t n_ptrs = 0, n_gl = 0;
+    std::vector<size_t> text_at;
+    for (int64_t s = 0; s < ns; ++s) {
+        const SiteOut& o = so[s];
+        if (o.n_alleles > HC_GT_MAX_ALLELES) continue;
+        const hc_gt_region& x = regions[o.region];
+        const char* ref = reinterpret_cast<const char*>(x.ref);
+        const size_t R = size_t(o.ref_len);
+        text_at.push_back(out.text.size());
+        out.text.insert(out.text.end(), ref + o.pos, ref + o.pos + R);
+        out.text.push_back('\0');
+        for (int32_t k = 0; k + 1 < o.n_alleles; ++k) {
+            const AltDesc& d = o.alt[k];
+            const char* own = hap_pool.data() + d.hap_off;
+            text_at.push_back(out.text.size());
+            if (d.kind == kAltStar) {
+                out.text.push_back('*');
+            } else if (d.kind == kAltSnp) {
+                out.text.push_back(*own);
+                out.text.insert(out.text.end(), ref + o.pos + 1, ref + o.pos + R);
+            } else if (d.kind == kAltIns) {
+                out.text.push_back(ref[o.pos]);
+                out.text.insert(out.text.end(), own, own + d.len);
+                out.text.insert(out.text.end(), ref + o.pos + 1, ref + o.pos + R);
+            } else {
+                out.text.push_back(ref[o.pos]);
+                out.text.insert(out.text.end(), ref + o.pos + d.len + 1, ref + o.pos + R);
+            }
+            out.text.push_back('\0');
+        }
+        n_ptrs += size_t(o.n_alleles);
+        n_gl += size_t(o.n_alleles * (o.n_alleles + 1) / 2);
+    }
+    out.ptrs.resize(n_ptrs);
+    out.gl.resize(n_gl);
+    for (size_t k = 0; k < n_ptrs; ++k) out.ptrs[k] = out.text.data() + text_at[k];
+    n_ptrs = n_gl = 0;
+    for (int64_t s = 0; s < ns; ++s) {
+        const SiteOut& o = so[s];
+        hc_gt_call_site& c = out.sites[size_t(s)];
+        c = hc_gt_call_site{};
+        c.region = o.region;
+        c.begin = regions[o.region].padded_begin + o.pos;
+        c.loc_end = c.begin + o.ref_len;
+        c.n_alleles = o.n_alleles;
+        c.genotype_index = c.a1 = c.a2 = c.genotype_quality = -1;
+        if (o.n_alleles > HC_GT_MAX_ALLELES) {
+            c.status = HC_GT_SITE_TOO_MANY_ALLELES;
+            continue;
+        }
+        const int32_t A = o.n_alleles, G = A * (A + 1) / 2;
+        c.n_haps = regions[o.region].n_haps;
+        c.alleles = out.ptrs.data() + n_ptrs;
+        c.hap_allele = amap + o.map_off;
+        c.keep = keep + o.keep_off;
+        c.n_keep = o.n_keep;
+        c.n_genotypes = G;
+        std::memcpy(out.gl.data() + n_gl, gl + s * kMaxGenotypes, sizeof(double) * size_t(G));
+        c.genotype_likelihoods = out.gl.data() + n_gl;
+        n_ptrs += size_t(A);
+        n_gl += size_t(G);
+        c.genotype_index = gi[s];
+        c.genotype_quality = gq[s];
+        int32_t a1 = 0, rem = gi[s];   // allele_index_cache: a1-major, a1 <= a2
+        while (rem >= A - a1) {
+            rem -= A - a1;
+            ++a1;
+        }
+        c.a1 = a1;
+        c.a2 = a1 + rem;
+        c.status = gi[s] == 0 ? HC_GT_SITE_HOM_REF
+                   : (a1 == 0 && gq[s] < 50) ? HC_GT_SITE_LOW_QUALITY_HET   // MIN_HETEROZYGOSITY_QUALITY
+                                             : HC_GT_SITE_EMITTED;
+    }
+    return HC_PHMM_OK;
+}
+
 }  // namespace
+
+struct hc_gt_calls {
+    Calls c;
+};
 
 extern "C" int hc_gt_genotype_sites(const hc_gt_site* sites, int32_t n_sites)
 {
@@ -219,6 +538,38 @@ extern "C" int hc_gt_genotype_sites(const hc_gt_site* sites, int32_t n_sites)
     return run(sites, n_sites);
 }
 
+extern "C" int hc_gt_call_regions(const hc_gt_region* regions, int32_t n_regions, hc_gt_calls** out)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!out) return fail(HC_PHMM_EINVAL, "null out");
+    *out = nullptr;
+    if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
+    int rc = ensure_init();
+    if (rc) return rc;
+    hc_gt_calls* calls = new hc_gt_calls();
+    if (n_regions) rc = run_regions(regions, n_regions, calls->c);
+    if (rc) {
+        delete calls;
+        return rc;
+    }
+    *out = calls;
+    return HC_PHMM_OK;
+}
+
+extern "C" int hc_gt_calls_sites(const hc_gt_calls* calls, const hc_gt_call_site** sites, int64_t* n)
+{
+    if (!calls || !sites || !n) return fail(HC_PHMM_EINVAL, "null argument");
+    *sites = calls->c.sites.data();
+    *n = int64_t(calls->c.sites.size());
+    return HC_PHMM_OK;
+}
+
+extern "C" int hc_gt_calls_free(hc_gt_calls* calls)
+{
+    delete calls;
+    return HC_PHMM_OK;
+}
+
 // Called by hc_phmm_shutdown.
 void hcphmm::gt_release()
 {
@@ -227,6 +578,9 @@ void hcphmm::gt_release()
     (void)hipStreamSynchronize(g_stream);
     if (g_jac) (void)hipFree(g_jac);
     if (g_dev) (void)hipFree(g_dev);
+    if (g_dev2) (void)hipFree(g_dev2);
+    g_dev2 = nullptr;
+    g_dev2_bytes = 0;
     if (g_host) (void)hipHostFree(g_host);
     (void)hipStreamDestroy(g_stream);
     g_stream = nullptr;

@@ -8,6 +8,11 @@ genotype_index) for many sites in one device pass. Sites are dicts
 read-major likelihood matrices ``mats`` (gt_workloads layout). Returns a list of
 (genotype_likelihoods float64[], genotype_index, genotype_quality).
 No CPU path: raises GTError without the library or a gfx950 device.
+
+``call_regions(regions)`` is the whole of assign_genotype_likelihoods: regions
+in (gt_workloads.regions layout), one dict per in-origin site out, with the
+events, alleles, haplotype -> allele map and kept reads computed on the device
+ahead of the same arithmetic.
 """
 from __future__ import annotations
 
@@ -35,6 +40,31 @@ class Site(C.Structure):
                 ("genotype_likelihoods", _f64p), ("genotype_index", _i32p), ("genotype_quality", _i32p)]
 
 
+class HapAln(C.Structure):
+    _fields_ = [("bases", C.c_char_p), ("length", C.c_int32), ("alignment_begin", C.c_int32), ("cigar", C.c_char_p)]
+
+
+_i64p = C.POINTER(C.c_int64)
+
+
+class Region(C.Structure):
+    _fields_ = [("ref", C.c_char_p), ("ref_len", C.c_int32), ("padded_begin", C.c_int64),
+                ("origin_begin", C.c_int64), ("origin_end", C.c_int64), ("haps", C.POINTER(HapAln)),
+                ("n_haps", C.c_int32), ("read_begin", _i64p), ("read_end", _i64p), ("n_reads", C.c_int32),
+                ("L", _f64p)]
+
+
+class CallSite(C.Structure):
+    _fields_ = [("region", C.c_int32), ("status", C.c_int32), ("begin", C.c_int64), ("loc_end", C.c_int64),
+                ("n_alleles", C.c_int32), ("n_haps", C.c_int32), ("alleles", C.POINTER(C.c_char_p)),
+                ("hap_allele", _i32p), ("keep", _i32p), ("n_keep", C.c_int32), ("n_genotypes", C.c_int32),
+                ("genotype_likelihoods", _f64p), ("genotype_index", C.c_int32), ("a1", C.c_int32),
+                ("a2", C.c_int32), ("genotype_quality", C.c_int32)]
+
+
+EMITTED, HOM_REF, LOW_QUALITY_HET, TOO_MANY_ALLELES = 0, 1, 2, 3
+MAX_HAPS, MAX_REF_LEN, MAX_HAP_LEN = 128, 1023, 1024
+
 _lib = None
 
 
@@ -43,6 +73,9 @@ def lib():
     if _lib is None:
         L = hcphmm.lib()
         L.hc_gt_genotype_sites.argtypes = [C.POINTER(Site), C.c_int32]
+        L.hc_gt_call_regions.argtypes = [C.POINTER(Region), C.c_int32, C.POINTER(C.c_void_p)]
+        L.hc_gt_calls_sites.argtypes = [C.c_void_p, C.POINTER(C.POINTER(CallSite)), _i64p]
+        L.hc_gt_calls_free.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -88,3 +121,69 @@ def genotype_sites(mats, sites):
     p = Prepared(mats, sites)
     p.run()
     return p.results()
+
+
+class PreparedRegions:
+    """The C structs of a call_regions call, built once (timing tools time run() alone)."""
+
+    def __init__(self, regions):
+        self.n = len(regions)
+        self.arr = (Region * max(self.n, 1))()
+        self.keep_alive = []
+        for k, r in enumerate(regions):
+            haps = (HapAln * max(len(r["haps"]), 1))()
+            for j, h in enumerate(r["haps"]):
+                haps[j] = HapAln(h["bases"], len(h["bases"]), int(h["begin"]), h["cigar"].encode())
+            rb = np.ascontiguousarray(r["read_begin"], np.int64)
+            re_ = np.ascontiguousarray(r["read_end"], np.int64)
+            L = np.ascontiguousarray(r["L"], np.float64)
+            self.keep_alive += [haps, rb, re_, L]
+            self.arr[k] = Region(r["ref"], len(r["ref"]), int(r["padded_begin"]), int(r["origin_begin"]),
+                                 int(r["origin_end"]), haps, len(r["haps"]),
+                                 rb.ctypes.data_as(_i64p) if len(rb) else None,
+                                 re_.ctypes.data_as(_i64p) if len(re_) else None, len(rb),
+                                 L.ctypes.data_as(_f64p) if L.size else None)
+
+    def run(self):
+        """One hc_gt_call_regions; returns the handle (free it with free())."""
+        h = C.c_void_p()
+        rc = lib().hc_gt_call_regions(self.arr, self.n, C.byref(h))
+        if rc != 0:
+            msg = lib().hc_phmm_last_error()
+            raise GTError(rc, msg.decode() if msg else "")
+        return h
+
+    @staticmethod
+    def free(h):
+        lib().hc_gt_calls_free(h)
+
+    @staticmethod
+    def records(h):
+        sites, n = C.POINTER(CallSite)(), C.c_int64()
+        rc = lib().hc_gt_calls_sites(h, C.byref(sites), C.byref(n))
+        if rc != 0:
+            raise GTError(rc, "hc_gt_calls_sites")
+        out = []
+        for k in range(n.value):
+            s = sites[k]
+            out.append(dict(
+                region=s.region, status=s.status, begin=s.begin, loc_end=s.loc_end, n_alleles=s.n_alleles,
+                alleles=[s.alleles[j] for j in range(s.n_alleles)] if s.alleles else [],
+                hap_allele=np.array(s.hap_allele[:s.n_haps], np.int32) if s.hap_allele else np.zeros(0, np.int32),
+                keep=np.array(s.keep[:s.n_keep], np.int32) if s.n_keep else np.zeros(0, np.int32),
+                genotype_likelihoods=np.array(s.genotype_likelihoods[:s.n_genotypes], np.float64)
+                if s.genotype_likelihoods else np.zeros(0, np.float64),
+                genotype_index=s.genotype_index, a1=s.a1, a2=s.a2, genotype_quality=s.genotype_quality))
+        return out
+
+
+def call_regions(regions):
+    """Site records (dicts) of every region: region, status, begin, loc_end,
+    n_alleles, alleles (bytes), hap_allele, keep, genotype_likelihoods,
+    genotype_index, a1, a2, genotype_quality."""
+    p = PreparedRegions(regions)
+    h = p.run()
+    try:
+        return p.records(h)
+    finally:
+        p.free(h)

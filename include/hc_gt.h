@@ -52,6 +52,87 @@ typedef struct hc_gt_site {
 
 int hc_gt_genotype_sites(const hc_gt_site* sites, int32_t n_sites);
 
+/*
+ * Whole drop-in for Genetyper::assign_genotype_likelihoods (:369-399): regions
+ * in, called variants out. The event bookkeeping runs on the device in the same
+ * pass as the arithmetic above:
+ *
+ *   process_cigar_for_initial_events  :35-111   SNP / insertion / deletion events of each
+ *                                               haplotype's CIGAR; the first event in CIGAR
+ *                                               order at a position wins (map emplace)
+ *   set_events_for_haplotypes         :113-127  sites = ascending event begins in the origin
+ *   get_events_from_haplotypes, replace_span_dels, get_compatible_alleles   :129-193
+ *   get_allele_mapper, get_haplotype_mapper, get_read_indices_to_keep       :195-243
+ *
+ * The host only parses and validates the CIGAR text. Where the reference reads
+ * out of bounds (a CIGAR that does not fit its haplotype or the window, an
+ * origin outside the window) the call returns HC_PHMM_EINVAL instead; an
+ * operator other than M I D S (the reference throws) is HC_PHMM_EINVAL too.
+ */
+#define HC_GT_MAX_REF_LEN 1023   /* = HC_SW_MAX_LEN1: the aligner's window limit */
+#define HC_GT_MAX_HAP_LEN 1024   /* = HC_SW_MAX_LEN2 */
+#define HC_GT_MAX_HAPS 128       /* per region; the reference's DEFAULT_NUM_PATHS */
+
+/* hc_gt_call_site.status */
+#define HC_GT_SITE_EMITTED 0           /* a variant of the reference's return value */
+#define HC_GT_SITE_HOM_REF 1           /* best genotype is 0/0 (:392) */
+#define HC_GT_SITE_LOW_QUALITY_HET 2   /* a1 == 0 and quality < 50 (:394) */
+#define HC_GT_SITE_TOO_MANY_ALLELES 3  /* more than HC_GT_MAX_ALLELES alleles (:386) */
+
+typedef struct hc_gt_hap_aln {
+    const uint8_t* bases;
+    int32_t length;           /* 1 .. HC_GT_MAX_HAP_LEN */
+    int32_t alignment_begin;  /* alignment_begin_wrt_ref, in window coordinates */
+    const char* cigar;        /* NUL-terminated "%d%c" runs of M I D S, as hc_sw writes them */
+} hc_gt_hap_aln;
+
+typedef struct hc_gt_region {
+    const uint8_t* ref;       /* the padded region's reference window */
+    int32_t ref_len;          /* 1 .. HC_GT_MAX_REF_LEN */
+    int64_t padded_begin;     /* contig coordinate of ref[0], >= 0 */
+    int64_t origin_begin;     /* padded_begin <= origin_begin <= origin_end <= padded_begin + ref_len */
+    int64_t origin_end;
+    const hc_gt_hap_aln* haps;
+    int32_t n_haps;           /* 1 .. HC_GT_MAX_HAPS; the index is the haplotype's rank */
+    const int64_t* read_begin; /* read intervals [begin, end), contig coordinates, >= 0 */
+    const int64_t* read_end;
+    int32_t n_reads;          /* >= 0 */
+    const double* L;          /* n_reads x n_haps, read-major (compute_likelihoods' return value) */
+} hc_gt_region;
+
+/* One record per event begin inside a region's origin, skipped sites included.
+ * For HC_GT_SITE_TOO_MANY_ALLELES the site is dropped before any map or
+ * arithmetic exists: n_alleles is HC_GT_MAX_ALLELES + 1 (counting stops there),
+ * alleles / hap_allele / keep / genotype_likelihoods are NULL with zero counts
+ * and genotype_index, a1, a2 and genotype_quality are -1. begin and loc_end are
+ * always valid. All pointers are owned by the hc_gt_calls handle. */
+typedef struct hc_gt_call_site {
+    int32_t region;
+    int32_t status;
+    int64_t begin;            /* alleles_loc.begin = the event begin (contig coordinate) */
+    int64_t loc_end;          /* alleles_loc.end = the largest event end at the site */
+    int32_t n_alleles;
+    int32_t n_haps;           /* length of hap_allele (0 when NULL) */
+    const char* const* alleles; /* n_alleles strings: the reference allele, then the alts sorted bytewise */
+    const int32_t* hap_allele;
+    const int32_t* keep;      /* ascending read indices overlapping [begin - 2, loc_end + 2) */
+    int32_t n_keep;
+    int32_t n_genotypes;      /* n_alleles * (n_alleles + 1) / 2 */
+    const double* genotype_likelihoods;
+    int32_t genotype_index;
+    int32_t a1, a2;           /* the genotype of genotype_index, a1 <= a2 */
+    int32_t genotype_quality;
+} hc_gt_call_site;
+
+typedef struct hc_gt_calls hc_gt_calls;
+
+/* One synchronous call on the engine's primary device. On success *out holds
+ * the sites of every region; release it with hc_gt_calls_free. */
+int hc_gt_call_regions(const hc_gt_region* regions, int32_t n_regions, hc_gt_calls** out);
+/* Every in-origin site, in region order then ascending begin. */
+int hc_gt_calls_sites(const hc_gt_calls* calls, const hc_gt_call_site** sites, int64_t* n);
+int hc_gt_calls_free(hc_gt_calls* calls);
+
 #ifdef __cplusplus
 }
 #endif
