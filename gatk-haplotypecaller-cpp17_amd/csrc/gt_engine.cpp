@@ -17,6 +17,7 @@
 
 #include "../../include/hc_gt.h"
 #include "../../include/hc_pairhmm.h"
+#include "gt_engine_internal.hpp"
 #include "gt_kernels.hpp"
 #include "gt_plan_kernels.hpp"
 #include "pool.hpp"
@@ -218,13 +219,8 @@ int run(const hc_gt_site* sites, int32_t n)
 
 // ---- hc_gt_call_regions: events, sites, alleles, maps and kept reads on the device ----
 
-struct Calls {
-    std::vector<hc_gt_call_site> sites;
-    std::vector<char> text;          // allele strings, NUL-terminated
-    std::vector<const char*> ptrs;   // per site, n_alleles pointers into text
-    std::vector<int32_t> ints;       // the downloaded keep and hap_allele blocks
-    std::vector<double> gl;
-};
+using hcgt_host::Calls;
+using hcgt_host::RegionView;
 
 // "%d%c" runs of M I D S, each with the window and haplotype position it starts at.
 bool parse_cigar(const char* t, int32_t begin, std::vector<PlanRun>& runs, int32_t& ref_pos, int32_t& hap_pos)
@@ -278,13 +274,10 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
     for (int32_t r = 0; r < n; ++r) {
         const hc_gt_region& x = regions[r];
         const std::string at = "region " + std::to_string(r);
-        if (!x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.L)))
-            return fail(HC_PHMM_EINVAL, at + ": null pointer");
-        if (x.ref_len < 1 || x.ref_len > HC_GT_MAX_REF_LEN || x.n_haps < 1 || x.n_haps > HC_GT_MAX_HAPS || x.n_reads < 0)
-            return fail(HC_PHMM_EINVAL, at + ": ref_len, n_haps or n_reads out of range");
-        if (x.padded_begin < 0 || x.origin_begin < x.padded_begin || x.origin_end < x.origin_begin ||
-            x.origin_end > x.padded_begin + x.ref_len)
-            return fail(HC_PHMM_EINVAL, at + ": origin outside the padded window");
+        if (int rc = hcgt_host::check_region_frame(
+                at, !x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.L)), x.ref_len, x.n_haps,
+                x.n_reads, x.padded_begin, x.origin_begin, x.origin_end))
+            return rc;
         PlanRegion& d = pr[size_t(r)];
         d.padded_begin = x.padded_begin;
         d.origin_begin = x.origin_begin;
@@ -299,21 +292,14 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
         for (int32_t h = 0; h < x.n_haps; ++h) {
             const hc_gt_hap_aln& y = x.haps[h];
             const std::string hat = at + " haplotype " + std::to_string(h);
-            if (!y.bases || !y.cigar) return fail(HC_PHMM_EINVAL, hat + ": null pointer");
-            if (y.length < 1 || y.length > HC_GT_MAX_HAP_LEN || y.alignment_begin < 0 || y.alignment_begin > x.ref_len)
-                return fail(HC_PHMM_EINVAL, hat + ": length or alignment_begin out of range");
+            if (int rc = hcgt_host::check_hap_frame(hat, !y.bases || !y.cigar, y.length, y.alignment_begin, x.ref_len))
+                return rc;
             PlanHap e;
             e.region = r;
             e.base_off = int32_t(hap_pool.size());
             e.run_off = int32_t(runs.size());
             e.tab_off = int32_t(tab_total);
-            int32_t ref_end = 0, hap_end = 0;
-            if (!parse_cigar(y.cigar, y.alignment_begin, runs, ref_end, hap_end))
-                return fail(HC_PHMM_EINVAL, hat + ": bad CIGAR '" + std::string(y.cigar).substr(0, 64) + "'");
-            if (hap_end != y.length)
-                return fail(HC_PHMM_EINVAL, hat + ": CIGAR consumes " + std::to_string(hap_end) + " bases of " +
-                                                std::to_string(y.length));
-            if (ref_end > x.ref_len) return fail(HC_PHMM_EINVAL, hat + ": CIGAR runs past the reference window");
+            if (int rc = hcgt_host::parse_hap_cigar(hat, y.cigar, y.alignment_begin, y.length, x.ref_len, runs)) return rc;
             e.n_runs = int32_t(runs.size()) - e.run_off;
             hap_pool.append(reinterpret_cast<const char*>(y.bases), size_t(y.length));
             ph.push_back(e);
@@ -435,22 +421,74 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
     HIP_TRY(launch_arithmetic(a));
     HIP_TRY(hipMemcpyAsync(h, g_dev2, back, hipMemcpyDeviceToHost, g_stream));
     HIP_TRY(hipStreamSynchronize(g_stream));
-    // Materialise the records: strings from the alt descriptors, pointers into the copied blocks.
-    const SiteOut* so = reinterpret_cast<const SiteOut*>(h + o_so);
-    const double* gl = reinterpret_cast<const double*>(h + o_gl);
-    const int32_t* gi = reinterpret_cast<const int32_t*>(h + o_gi);
-    const int32_t* gq = reinterpret_cast<const int32_t*>(h + o_gq);
-    out.ints.resize(size_t(tot.keep_cap + tot.map_cap));
-    std::memcpy(out.ints.data(), h + o_keep, sizeof(int32_t) * out.ints.size());
-    const int32_t* keep = out.ints.data();
-    const int32_t* amap = out.ints.data() + tot.keep_cap;
+    std::vector<RegionView> views(static_cast<size_t>(n));
+    for (int32_t r = 0; r < n; ++r) views[size_t(r)] = RegionView{regions[r].ref, regions[r].padded_begin, regions[r].n_haps};
+    hcgt_host::materialise(views.data(), hap_pool.data(), reinterpret_cast<const SiteOut*>(h + o_so), ns,
+                           reinterpret_cast<const double*>(h + o_gl), reinterpret_cast<const int32_t*>(h + o_gi),
+                           reinterpret_cast<const int32_t*>(h + o_gq), reinterpret_cast<const int32_t*>(h + o_keep),
+                           tot.keep_cap, reinterpret_cast<const int32_t*>(h + o_map), tot.map_cap, out);
+    return HC_PHMM_OK;
+}
+
+}  // namespace
+
+namespace hcgt_host {
+
+std::mutex& mutex() { return g_mu; }
+int ensure_init() { return ::ensure_init(); }
+hipStream_t stream() { return g_stream; }
+hipError_t launch_arithmetic(hcgt::GtArgs& a) { return ::launch_arithmetic(a); }
+
+int check_region_frame(const std::string& at, bool null_pointer, int32_t ref_len, int32_t n_haps, int32_t n_reads,
+                       int64_t padded_begin, int64_t origin_begin, int64_t origin_end)
+{
+    if (null_pointer) return fail(HC_PHMM_EINVAL, at + ": null pointer");
+    if (ref_len < 1 || ref_len > HC_GT_MAX_REF_LEN || n_haps < 1 || n_haps > HC_GT_MAX_HAPS || n_reads < 0)
+        return fail(HC_PHMM_EINVAL, at + ": ref_len, n_haps or n_reads out of range");
+    if (padded_begin < 0 || origin_begin < padded_begin || origin_end < origin_begin || origin_end > padded_begin + ref_len)
+        return fail(HC_PHMM_EINVAL, at + ": origin outside the padded window");
+    return HC_PHMM_OK;
+}
+
+int check_hap_frame(const std::string& hat, bool null_pointer, int32_t length, int32_t alignment_begin, int32_t ref_len)
+{
+    if (null_pointer) return fail(HC_PHMM_EINVAL, hat + ": null pointer");
+    if (length < 1 || length > HC_GT_MAX_HAP_LEN || alignment_begin < 0 || alignment_begin > ref_len)
+        return fail(HC_PHMM_EINVAL, hat + ": length or alignment_begin out of range");
+    return HC_PHMM_OK;
+}
+
+int parse_hap_cigar(const std::string& hat, const char* cigar, int32_t alignment_begin, int32_t length, int32_t ref_len,
+                    std::vector<hcgt::PlanRun>& runs)
+{
+    int32_t ref_end = 0, hap_end = 0;
+    if (!parse_cigar(cigar, alignment_begin, runs, ref_end, hap_end))
+        return fail(HC_PHMM_EINVAL, hat + ": bad CIGAR '" + std::string(cigar).substr(0, 64) + "'");
+    if (hap_end != length)
+        return fail(HC_PHMM_EINVAL, hat + ": CIGAR consumes " + std::to_string(hap_end) + " bases of " +
+                                        std::to_string(length));
+    if (ref_end > ref_len) return fail(HC_PHMM_EINVAL, hat + ": CIGAR runs past the reference window");
+    return HC_PHMM_OK;
+}
+
+// Strings from the alt descriptors, pointers into the copied blocks.
+void materialise(const RegionView* regions, const char* hap_pool, const hcgt::SiteOut* so, int64_t ns, const double* gl,
+                 const int32_t* gi, const int32_t* gq, const int32_t* keep_in, int64_t keep_cap, const int32_t* amap_in,
+                 int64_t map_cap, Calls& out)
+{
+    const size_t nk = keep_in ? size_t(keep_cap) : 0;
+    out.ints.resize(nk + size_t(map_cap));
+    if (nk) std::memcpy(out.ints.data(), keep_in, sizeof(int32_t) * nk);
+    if (map_cap) std::memcpy(out.ints.data() + nk, amap_in, sizeof(int32_t) * size_t(map_cap));
+    const int32_t* keep = keep_in ? out.ints.data() : nullptr;
+    const int32_t* amap = out.ints.data() + nk;
     out.sites.resize(size_t(ns));
     size_t n_ptrs = 0, n_gl = 0;
     std::vector<size_t> text_at;
     for (int64_t s = 0; s < ns; ++s) {
         const SiteOut& o = so[s];
         if (o.n_alleles > HC_GT_MAX_ALLELES) continue;
-        const hc_gt_region& x = regions[o.region];
+        const RegionView& x = regions[o.region];
         const char* ref = reinterpret_cast<const char*>(x.ref);
         const size_t R = size_t(o.ref_len);
         text_at.push_back(out.text.size());
@@ -458,7 +496,7 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
         out.text.push_back('\0');
         for (int32_t k = 0; k + 1 < o.n_alleles; ++k) {
             const AltDesc& d = o.alt[k];
-            const char* own = hap_pool.data() + d.hap_off;
+            const char* own = hap_pool + d.hap_off;
             text_at.push_back(out.text.size());
             if (d.kind == kAltStar) {
                 out.text.push_back('*');
@@ -499,8 +537,8 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
         c.n_haps = regions[o.region].n_haps;
         c.alleles = out.ptrs.data() + n_ptrs;
         c.hap_allele = amap + o.map_off;
-        c.keep = keep + o.keep_off;
-        c.n_keep = o.n_keep;
+        c.keep = keep ? keep + o.keep_off : nullptr;
+        c.n_keep = keep ? o.n_keep : 0;
         c.n_genotypes = G;
         std::memcpy(out.gl.data() + n_gl, gl + s * kMaxGenotypes, sizeof(double) * size_t(G));
         c.genotype_likelihoods = out.gl.data() + n_gl;
@@ -519,10 +557,9 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
                    : (a1 == 0 && gq[s] < 50) ? HC_GT_SITE_LOW_QUALITY_HET   // MIN_HETEROZYGOSITY_QUALITY
                                              : HC_GT_SITE_EMITTED;
     }
-    return HC_PHMM_OK;
 }
 
-}  // namespace
+}  // namespace hcgt_host
 
 struct hc_gt_calls {
     Calls c;

@@ -22,6 +22,7 @@
 
 #include "../../include/hc_pairhmm.h"
 #include "../../include/hc_sw.h"
+#include "sw_engine_internal.hpp"
 #include "sw_kernels.hpp"
 
 namespace hcphmm {
@@ -193,7 +194,7 @@ int create(int64_t n, const int64_t* ref_off, const int32_t* ref_len, const uint
 
     std::vector<SwPair> pairs;
     pairs.reserve(static_cast<size_t>(n));
-    int64_t ref_ext = 0, alt_ext = 0, bt_total = 0, el_total = 0;
+    int64_t ref_ext = 0, alt_ext = 0;
     for (int64_t k = 0; k < n; ++k) {
         const int n1 = ref_len[k], n2 = alt_len[k];
         const bool in_range = n1 >= 1 && n2 >= 1 && n1 <= HC_SW_MAX_LEN1 && n2 <= HC_SW_MAX_LEN2;
@@ -216,34 +217,21 @@ int create(int64_t n, const int64_t* ref_off, const int32_t* ref_len, const uint
         P.alt_off = alt_off[k];
         P.n1 = n1;
         P.n2 = n2;
-        P.el_off = el_total;
-        el_total += n1 + n2 + 3;
         ref_ext = std::max(ref_ext, ref_off[k] + n1);
         alt_ext = std::max(alt_ext, alt_off[k] + n2);
-        b->n1max = std::max(b->n1max, n1);
-        b->n2max = std::max(b->n2max, n2);
-        b->cells += int64_t(n1) * n2;
         pairs.push_back(P);
         b->dev_ids.push_back(k);
     }
     n = int64_t(pairs.size());
     b->nd = n;
-    // Longest pairs first: the tail of the launch is made of short waves.
-    std::vector<int32_t> order(static_cast<size_t>(n));
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-        return int64_t(pairs[x].n1) * pairs[x].n2 > int64_t(pairs[y].n1) * pairs[y].n2;
-    });
+    const hcsw_host::PairLayout lay = hcsw_host::layout_pairs(pairs);
+    const std::vector<int32_t>& order = lay.order;
+    const int64_t bt_total = lay.bt_total, el_total = lay.el_total;
+    b->n1max = lay.n1max;
+    b->n2max = lay.n2max;
+    b->cells = lay.cells;
     b->n_el_cap = el_total;
-    b->fast = fast_ok(params, overhang, b->n1max, b->n2max) ? 1 : 0;
-    if (const char* e = std::getenv("HC_SW_GENERIC"))   // parity tests of the generic variant
-        if (e[0] == '1') b->fast = 0;
-    // (An LDS substitution profile and a spiral layout of the fast path were
-    // measured slower — W2 DP 10.8 / 9.33 vs 8.72 ms — and removed, round 6.)
-    for (auto& P : pairs) {
-        P.bt_off = bt_total;
-        bt_total += bt_words(P.n1, P.n2);
-    }
+    b->fast = hcsw_host::dp_variant(params, overhang, b->n1max, b->n2max);
 
     // One device allocation: descriptors, inputs, outputs, scratch.
     size_t off = 0;
@@ -323,45 +311,25 @@ int run(hc_sw_batch* b, hipStream_t s)
         b->ran = true;
         return HC_SW_OK;
     }
-    SwDpArgs d{};
+    hcsw_host::DeviceBatch d;
+    d.n = b->nd;
     d.pairs = b->pairs;
     d.order = b->order;
-    d.n = int(b->nd);
     d.refs = b->refs;
     d.alts = b->alts;
-    d.bt = b->bt;
     d.res = b->res;
+    d.bt = b->bt;
     d.elems = b->elems;
-    d.match = b->params.match;
-    d.mismatch = b->params.mismatch;
-    d.open = b->params.open;
-    d.extend = b->params.extend;
+    d.slots = b->slots;
+    d.n_elems = b->n_elems;
+    d.offsets = b->offsets;
+    d.params = b->params;
     d.overhang = b->overhang;
     d.shortcut = b->shortcut;
+    d.fast = b->fast;
     d.n1max = b->n1max;
     d.n2max = b->n2max;
-    d.fast = b->fast;
-    // Pairs per workgroup: one for region-sized windows (W2, n2 <= ~650: 8.62 /
-    // 9.09 / 9.20 ms at 1 / 2 / 4), four for long ones (W3, n2 ~ 1000: 3.54 /
-    // 3.25 / 2.90 ms); HC_SW_WPG overrides.
-    d.wpg = b->n2max > 800 ? 4 : 1;
-    if (const char* e = std::getenv("HC_SW_WPG"))
-        if (std::atoi(e) > 0) d.wpg = std::atoi(e);
-    SwTraceArgs t{};
-    t.pairs = b->pairs;
-    t.res = b->res;
-    t.bt = b->bt;
-    t.n = int(b->nd);
-    t.overhang = b->overhang;
-    t.elems = b->elems;
-    t.slots = b->slots;
-    t.n_elems = b->n_elems;
-    t.offsets = b->offsets;
-    HIP_TRY(hipEventRecord(b->ev[0], s));
-    HIP_TRY(launch_dp(d, b->n1max, s));
-    HIP_TRY(hipEventRecord(b->ev[1], s));
-    HIP_TRY(launch_trace(t, s));
-    HIP_TRY(hipEventRecord(b->ev[2], s));
+    HIP_TRY(hcsw_host::launch_batch(d, s, b->ev));
     HIP_TRY(hipEventSynchronize(b->ev[2]));
     float a = 0, c = 0, w = 0;
     HIP_TRY(hipEventElapsedTime(&a, b->ev[0], b->ev[1]));
@@ -455,6 +423,88 @@ int results(hc_sw_batch* b, int32_t* offsets, char* cigars, int32_t stride, int3
 }
 
 }  // namespace
+
+namespace hcsw_host {
+
+PairLayout layout_pairs(std::vector<SwPair>& pairs)
+{
+    PairLayout lay;
+    for (auto& P : pairs) {
+        P.el_off = lay.el_total;
+        lay.el_total += P.n1 + P.n2 + 3;
+        lay.n1max = std::max(lay.n1max, P.n1);
+        lay.n2max = std::max(lay.n2max, P.n2);
+        lay.cells += int64_t(P.n1) * P.n2;
+    }
+    // Longest pairs first: the tail of the launch is made of short waves.
+    lay.order.resize(pairs.size());
+    std::iota(lay.order.begin(), lay.order.end(), 0);
+    std::stable_sort(lay.order.begin(), lay.order.end(), [&](int32_t x, int32_t y) {
+        return int64_t(pairs[x].n1) * pairs[x].n2 > int64_t(pairs[y].n1) * pairs[y].n2;
+    });
+    for (auto& P : pairs) {
+        P.bt_off = lay.bt_total;
+        lay.bt_total += bt_words(P.n1, P.n2);
+    }
+    return lay;
+}
+
+int dp_variant(const hc_sw_params& params, int overhang, int n1max, int n2max)
+{
+    int fast = fast_ok(params, overhang, n1max, n2max) ? 1 : 0;
+    if (const char* e = std::getenv("HC_SW_GENERIC"))   // parity tests of the generic variant
+        if (e[0] == '1') fast = 0;
+    // (An LDS substitution profile and a spiral layout of the fast path were
+    // measured slower — W2 DP 10.8 / 9.33 vs 8.72 ms — and removed, round 6.)
+    return fast;
+}
+
+hipError_t launch_batch(const DeviceBatch& b, hipStream_t s, hipEvent_t* ev)
+{
+    SwDpArgs d{};
+    d.pairs = b.pairs;
+    d.order = b.order;
+    d.n = int(b.n);
+    d.refs = b.refs;
+    d.alts = b.alts;
+    d.bt = b.bt;
+    d.res = b.res;
+    d.elems = b.elems;
+    d.match = b.params.match;
+    d.mismatch = b.params.mismatch;
+    d.open = b.params.open;
+    d.extend = b.params.extend;
+    d.overhang = b.overhang;
+    d.shortcut = b.shortcut;
+    d.n1max = b.n1max;
+    d.n2max = b.n2max;
+    d.fast = b.fast;
+    // Pairs per workgroup: one for region-sized windows (W2, n2 <= ~650: 8.62 /
+    // 9.09 / 9.20 ms at 1 / 2 / 4), four for long ones (W3, n2 ~ 1000: 3.54 /
+    // 3.25 / 2.90 ms); HC_SW_WPG overrides.
+    d.wpg = b.n2max > 800 ? 4 : 1;
+    if (const char* e = std::getenv("HC_SW_WPG"))
+        if (std::atoi(e) > 0) d.wpg = std::atoi(e);
+    SwTraceArgs t{};
+    t.pairs = b.pairs;
+    t.res = b.res;
+    t.bt = b.bt;
+    t.n = int(b.n);
+    t.overhang = b.overhang;
+    t.elems = b.elems;
+    t.slots = b.slots;
+    t.n_elems = b.n_elems;
+    t.offsets = b.offsets;
+    hipError_t e = hipSuccess;
+    if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
+    if ((e = launch_dp(d, b.n1max, s)) != hipSuccess) return e;
+    if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+    if ((e = launch_trace(t, s)) != hipSuccess) return e;
+    if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+}  // namespace hcsw_host
 
 extern "C" {
 
