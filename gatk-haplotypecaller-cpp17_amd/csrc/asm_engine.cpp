@@ -10,16 +10,15 @@
 //     then the on-path edges that were written
 //   per region on the worker pool: paths, scores, sort and bytes (asm_paths.cpp)
 //
-// The workspace is the engine's own (grow-only, released by hc_phmm_shutdown).
+// The workspace is the engine's own: six grow-only buffers of the shared host
+// layer (stage_host.hpp, with the carver, the trace and HIP_TRY), released by
+// hc_phmm_shutdown. A HIP error drains the assembler's stream before it returns.
 // Calls serialise under the assembler's own lock and use the engine's primary
 // device. HC_ASM_TRACE=1 prints the host wall clock of the phases on stderr, and
 // from the device's own clock the share of the single-thread threading.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -31,14 +30,15 @@
 #include "asm_kernels.hpp"
 #include "asm_paths.hpp"
 #include "pool.hpp"
+#include "stage_host.hpp"
 
 namespace hcphmm {
-void set_last_error(const std::string& msg);
 int primary_device();
 void asm_release();
 }
 
 using namespace hcasm;
+using namespace stage_host;
 
 namespace {
 
@@ -47,98 +47,18 @@ hipStream_t g_stream = nullptr;
 int g_cus = 0;
 int g_clock_khz = 0;   // of wall_clock64(), for the trace
 
-struct Buf {
-    char* p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-};
 Buf g_in, g_seg, g_work, g_out, g_hin{nullptr, 0, true}, g_hback{nullptr, 0, true};
-
-int fail(int code, const std::string& msg)
-{
-    hcphmm::set_last_error(msg);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            if (g_stream) (void)hipStreamSynchronize(g_stream);                           \
-            return fail(HC_PHMM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-        }                                                                                 \
-    } while (0)
-
-void drop(Buf& b)
-{
-    if (b.p) (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-int reserve(Buf& b, size_t bytes, const char* what)
-{
-    if (bytes <= b.bytes) return HC_PHMM_OK;
-    drop(b);
-    const size_t want = bytes + bytes / 4;
-    const hipError_t e = b.pinned ? hipHostMalloc(reinterpret_cast<void**>(&b.p), want, hipHostMallocDefault)
-                                  : hipMalloc(reinterpret_cast<void**>(&b.p), want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return fail(HC_PHMM_ENOMEM, std::string("assembler ") + what);
-    }
-    b.bytes = want;
-    return HC_PHMM_OK;
-}
-
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t at = off;
-        off = asm_up(off + std::max<size_t>(bytes, 1));
-        return at;
-    }
-};
-
-// HC_ASM_TRACE=1: host wall clock of a call's phases on stderr (ms since the call began).
-struct Trace {
-    bool on = false;
-    std::chrono::steady_clock::time_point t0;
-    std::string line;
-    Trace()
-    {
-        const char* e = std::getenv("HC_ASM_TRACE");
-        on = e && e[0] == '1';
-        if (on) t0 = std::chrono::steady_clock::now();
-    }
-    void mark(const char* what)
-    {
-        if (on) value(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    }
-    void value(const char* what, double x)
-    {
-        if (!on) return;
-        char tmp[64];
-        std::snprintf(tmp, sizeof(tmp), " %s=%.3f", what, x);
-        line += tmp;
-    }
-    ~Trace()
-    {
-        if (on) std::fprintf(stderr, "[hc_asm]%s\n", line.c_str());
-    }
-};
 
 int ensure_init()
 {
     const int rc = hc_phmm_init(0, -1);
     if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(hipSetDevice(hcphmm::primary_device()));
+    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
     if (g_stream) return HC_PHMM_OK;
-    HIP_TRY(hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, hcphmm::primary_device()));
+    HIP_TRY(g_stream, hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, hcphmm::primary_device()));
     if (hipDeviceGetAttribute(&g_clock_khz, hipDeviceAttributeWallClockRate, hcphmm::primary_device()) != hipSuccess)
         g_clock_khz = 0;
-    HIP_TRY(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
+    HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
     return HC_PHMM_OK;
 }
 
@@ -173,7 +93,7 @@ int validate(const hc_asm_region* regions, int32_t n)
 
 int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& res)
 {
-    Trace tr;
+    Trace tr("HC_ASM_TRACE", "[hc_asm]");
     // ---- layout
     int64_t n_seqs = 0, pool = 0;
     int32_t max_bases = 1, max_hash = 64, max_cap = 1;
@@ -209,9 +129,9 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     const size_t o_bases = in.take(size_t(pool));
     const size_t o_quals = in.take(size_t(pool));
     const size_t in_bytes = in.off;
-    int rc = reserve(g_hin, in_bytes, "staging");
+    int rc = reserve(g_hin, in_bytes, "assembler staging");
     if (rc) return rc;
-    rc = reserve(g_in, in_bytes, "input");
+    rc = reserve(g_in, in_bytes, "assembler input");
     if (rc) return rc;
     char* h = g_hin.p;
     std::memcpy(h + o_reg, regs.data(), sizeof(AsmRegion) * size_t(n));
@@ -254,9 +174,9 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     // ---- device buffers
     const int n_slots = std::max(1, std::min<int>(n, 2 * std::max(g_cus, 1)));
     const size_t slot_bytes = asm_slot_bytes(max_bases, max_hash, max_cap);
-    rc = reserve(g_seg, 2 * asm_up(sizeof(int32_t) * size_t(pool)), "segments");
+    rc = reserve(g_seg, 2 * up(sizeof(int32_t) * size_t(pool)), "assembler segments");
     if (rc) return rc;
-    rc = reserve(g_work, slot_bytes * size_t(n_slots), "workspace");
+    rc = reserve(g_work, slot_bytes * size_t(n_slots), "assembler workspace");
     if (rc) return rc;
     Carver oc;   // the tail that is read back first, then the edges
     const size_t o_out = oc.take(sizeof(AsmOut) * size_t(n));
@@ -264,9 +184,9 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     const size_t o_err = oc.take(sizeof(int32_t) * 2);
     const size_t head_bytes = oc.off;
     const size_t o_edges = oc.take(sizeof(hc_asm_edge) * size_t(edge_cap));
-    rc = reserve(g_out, oc.off, "output");
+    rc = reserve(g_out, oc.off, "assembler output");
     if (rc) return rc;
-    rc = reserve(g_hback, oc.off, "readback");
+    rc = reserve(g_hback, oc.off, "assembler readback");
     if (rc) return rc;
 
     AsmArgs a{};
@@ -277,7 +197,7 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     a.bases = reinterpret_cast<const uint8_t*>(g_in.p + o_bases);
     a.quals = reinterpret_cast<const uint8_t*>(g_in.p + o_quals);
     a.rem = reinterpret_cast<int32_t*>(g_seg.p);
-    a.seg_start = reinterpret_cast<int32_t*>(g_seg.p + asm_up(sizeof(int32_t) * size_t(pool)));
+    a.seg_start = reinterpret_cast<int32_t*>(g_seg.p + up(sizeof(int32_t) * size_t(pool)));
     a.work = g_work.p;
     a.slot_bytes = slot_bytes;
     a.max_bases = max_bases;
@@ -289,21 +209,21 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     a.edge_pool_used = reinterpret_cast<unsigned long long*>(g_out.p + o_used);
     a.err = reinterpret_cast<int32_t*>(g_out.p + o_err);
 
-    HIP_TRY(hipMemcpyAsync(g_in.p, h, in_bytes, hipMemcpyHostToDevice, g_stream));
-    HIP_TRY(hipMemsetAsync(g_out.p + o_used, 0, head_bytes - o_used, g_stream));
+    HIP_TRY(g_stream, hipMemcpyAsync(g_in.p, h, in_bytes, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(g_stream, hipMemsetAsync(g_out.p + o_used, 0, head_bytes - o_used, g_stream));
     if (tr.on) {
-        HIP_TRY(hipStreamSynchronize(g_stream));
+        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
         tr.mark("upload");
     }
-    HIP_TRY(launch_asm_segments(a, g_stream));
-    HIP_TRY(launch_asm_graph(a, n_slots, g_stream));
+    HIP_TRY(g_stream, launch_asm_segments(a, g_stream));
+    HIP_TRY(g_stream, launch_asm_graph(a, n_slots, g_stream));
     if (tr.on) {
-        HIP_TRY(hipStreamSynchronize(g_stream));
+        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
         tr.mark("graph");
     }
     char* hb = g_hback.p;
-    HIP_TRY(hipMemcpyAsync(hb, g_out.p, head_bytes, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(g_stream, hipMemcpyAsync(hb, g_out.p, head_bytes, hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
     int32_t err[2];
     std::memcpy(err, hb + o_err, sizeof(err));
     if (err[0] != kErrNone)
@@ -313,9 +233,9 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     std::memcpy(&used, hb + o_used, sizeof(used));
     if (used > static_cast<unsigned long long>(edge_cap)) return fail(HC_PHMM_EHIP, "assembler: edge count out of its bound");
     if (used) {
-        HIP_TRY(hipMemcpyAsync(hb + o_edges, g_out.p + o_edges, sizeof(hc_asm_edge) * size_t(used), hipMemcpyDeviceToHost,
+        HIP_TRY(g_stream, hipMemcpyAsync(hb + o_edges, g_out.p + o_edges, sizeof(hc_asm_edge) * size_t(used), hipMemcpyDeviceToHost,
                                g_stream));
-        HIP_TRY(hipStreamSynchronize(g_stream));
+        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
     }
     tr.mark("readback");
 

@@ -4,7 +4,13 @@
 // likelihood matrices are uploaded once each (sites of a region share it),
 // with the kept-read lists and haplotype -> allele maps, in one H2D from a
 // pinned staging block; one launch of gt_sites_kernel; one D2H of the genotype
-// likelihoods, indices and qualities.
+// likelihoods, indices and qualities. hc_gt_call_regions plans the sites on the
+// device first (events, scan, the counted readback, then the site kernel).
+//
+// Three grow-only buffers of the shared host layer (stage_host.hpp): device,
+// site (sized by the counted readback) and pinned; every layout is written with
+// its Carver, and a HIP error drains the genotyper's stream before it returns.
+// What hc_region_call shares with this file is in gt_engine_internal.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,76 +27,40 @@
 #include "gt_kernels.hpp"
 #include "gt_plan_kernels.hpp"
 #include "pool.hpp"
+#include "stage_host.hpp"
 
 // MathUtils Jacobian table as g++ folds it at compile time (tools/gen_jacobian.py).
 #include "math_jacobian.inc"
 
 namespace hcphmm {
-void set_last_error(const std::string& msg);
 int primary_device();
 void gt_release();
 }
 
 using namespace hcgt;
+using namespace stage_host;
 
 namespace {
 
 std::mutex g_mu;
 hipStream_t g_stream = nullptr;
 double* g_jac = nullptr;
-char* g_dev = nullptr;
-size_t g_dev_bytes = 0;
-char* g_host = nullptr;
-size_t g_host_bytes = 0;
-
-int fail(int code, const std::string& msg)
-{
-    hcphmm::set_last_error(msg);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(HC_PHMM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+// Grow-only workspaces: sized by the input, by the site count, and the pinned image of either.
+Buf g_dev, g_dev2, g_host{nullptr, 0, true};
 
 // Runs on the engine's first device slot, made current on the calling thread.
 int ensure_init()
 {
     const int rc = hc_phmm_init(0, -1);
     if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(hipSetDevice(hcphmm::primary_device()));
+    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
     if (g_stream) return HC_PHMM_OK;
-    HIP_TRY(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&g_jac, sizeof(double) * kJacobianLen));
+    HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
+    HIP_TRY(g_stream, hipMalloc(&g_jac, sizeof(double) * kJacobianLen));
     static_assert(sizeof(kMathJacobianBits) == sizeof(double) * kJacobianLen, "table length");
-    HIP_TRY(hipMemcpy(g_jac, kMathJacobianBits, sizeof(double) * kJacobianLen, hipMemcpyHostToDevice));
+    HIP_TRY(g_stream, hipMemcpy(g_jac, kMathJacobianBits, sizeof(double) * kJacobianLen, hipMemcpyHostToDevice));
     return HC_PHMM_OK;
 }
-
-int reserve(size_t dev, size_t host)
-{
-    if (dev > g_dev_bytes) {
-        if (g_dev) (void)hipFree(g_dev);
-        g_dev = nullptr;
-        g_dev_bytes = 0;
-        if (hipMalloc(&g_dev, dev + dev / 4) != hipSuccess) return fail(HC_PHMM_ENOMEM, "genotyper device workspace");
-        g_dev_bytes = dev + dev / 4;
-    }
-    if (host > g_host_bytes) {
-        if (g_host) (void)hipHostFree(g_host);
-        g_host = nullptr;
-        g_host_bytes = 0;
-        if (hipHostMalloc(&g_host, host + host / 4, hipHostMallocDefault) != hipSuccess)
-            return fail(HC_PHMM_ENOMEM, "genotyper pinned workspace");
-        g_host_bytes = host + host / 4;
-    }
-    return HC_PHMM_OK;
-}
-
-size_t up(size_t x) { return (x + 255) & ~size_t(255); }
 
 // The one launch of the arithmetic, shared by hc_gt_genotype_sites (records,
 // keep lists and maps uploaded) and hc_gt_call_regions (written on the device).
@@ -150,20 +120,23 @@ int run(const hc_gt_site* sites, int32_t n)
             return fail(HC_PHMM_EINVAL, "too many sites for one call");
     }
     // Layout: [sites | L | keep | amap] uploaded, then [gl | gi | gq] read back, then scratch.
-    const size_t o_sites = 0;
-    const size_t o_L = up(o_sites + sizeof(GtSite) * size_t(n));
-    const size_t o_keep = up(o_L + sizeof(double) * size_t(L_total));
-    const size_t o_map = up(o_keep + sizeof(int32_t) * size_t(keep_total));
-    const size_t in_bytes = up(o_map + sizeof(int32_t) * size_t(map_total));
-    const size_t o_gl = in_bytes;
-    const size_t o_gi = up(o_gl + sizeof(double) * size_t(out_total));
-    const size_t o_gq = up(o_gi + sizeof(int32_t) * size_t(n));
-    const size_t o_al = up(o_gq + sizeof(int32_t) * size_t(n));
-    const size_t tail = o_al - o_gl;
-    const size_t dev_bytes = up(o_al + sizeof(double) * size_t(std::max<int64_t>(al_total, 1)));
-    int rc = reserve(dev_bytes, std::max(in_bytes, tail));
+    Carver cv;
+    const size_t o_sites = cv.take(sizeof(GtSite) * size_t(n));
+    const size_t o_L = cv.take(sizeof(double) * size_t(L_total));
+    const size_t o_keep = cv.take(sizeof(int32_t) * size_t(keep_total));
+    const size_t o_map = cv.take(sizeof(int32_t) * size_t(map_total));
+    const size_t in_bytes = cv.off;
+    const size_t o_gl = cv.take(sizeof(double) * size_t(out_total));
+    const size_t o_gi = cv.take(sizeof(int32_t) * size_t(n));
+    const size_t o_gq = cv.take(sizeof(int32_t) * size_t(n));
+    const size_t tail = cv.off - o_gl;
+    const size_t o_al = cv.take(sizeof(double) * size_t(al_total));
+    int rc = reserve(g_dev, cv.off, "genotyper device workspace");
     if (rc) return rc;
-    char* h = g_host;
+    rc = reserve(g_host, std::max(in_bytes, tail), "genotyper pinned workspace");
+    if (rc) return rc;
+    char* const h = g_host.p;
+    char* const dv = g_dev.p;
     std::memcpy(h + o_sites, ds.data(), sizeof(GtSite) * size_t(n));
     // The likelihood matrices dominate the upload (512 regions of 415 x 32:
     // 54 MB): staged by the engine's worker pool, in slices so each slice's
@@ -181,7 +154,7 @@ int run(const hc_gt_site* sites, int32_t n)
             }
         }, 1);
         const size_t end = m1 < nm ? o_L + sizeof(double) * size_t(mat_off[size_t(m1)]) : o_keep;
-        HIP_TRY(hipMemcpyAsync(g_dev + sent, h + sent, end - sent, hipMemcpyHostToDevice, g_stream));
+        HIP_TRY(g_stream, hipMemcpyAsync(dv + sent, h + sent, end - sent, hipMemcpyHostToDevice, g_stream));
         sent = end;
     }
     for (int32_t s = 0; s < n; ++s) {
@@ -189,20 +162,20 @@ int run(const hc_gt_site* sites, int32_t n)
         if (x.n_keep) std::memcpy(h + o_keep + sizeof(int32_t) * size_t(ds[size_t(s)].keep_off), x.keep, sizeof(int32_t) * size_t(x.n_keep));
         std::memcpy(h + o_map + sizeof(int32_t) * size_t(ds[size_t(s)].map_off), x.hap_allele, sizeof(int32_t) * size_t(x.n_haps));
     }
-    HIP_TRY(hipMemcpyAsync(g_dev + sent, h + sent, in_bytes - sent, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(g_stream, hipMemcpyAsync(dv + sent, h + sent, in_bytes - sent, hipMemcpyHostToDevice, g_stream));
     GtArgs a{};
-    a.sites = reinterpret_cast<const GtSite*>(g_dev + o_sites);
+    a.sites = reinterpret_cast<const GtSite*>(dv + o_sites);
     a.n = n;
-    a.L = reinterpret_cast<const double*>(g_dev + o_L);
-    a.keep = reinterpret_cast<const int32_t*>(g_dev + o_keep);
-    a.amap = reinterpret_cast<const int32_t*>(g_dev + o_map);
-    a.al = reinterpret_cast<double*>(g_dev + o_al);
-    a.gl = reinterpret_cast<double*>(g_dev + o_gl);
-    a.gi = reinterpret_cast<int32_t*>(g_dev + o_gi);
-    a.gq = reinterpret_cast<int32_t*>(g_dev + o_gq);
-    HIP_TRY(launch_arithmetic(a));
-    HIP_TRY(hipMemcpyAsync(h, g_dev + o_gl, tail, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
+    a.L = reinterpret_cast<const double*>(dv + o_L);
+    a.keep = reinterpret_cast<const int32_t*>(dv + o_keep);
+    a.amap = reinterpret_cast<const int32_t*>(dv + o_map);
+    a.al = reinterpret_cast<double*>(dv + o_al);
+    a.gl = reinterpret_cast<double*>(dv + o_gl);
+    a.gi = reinterpret_cast<int32_t*>(dv + o_gi);
+    a.gq = reinterpret_cast<int32_t*>(dv + o_gq);
+    HIP_TRY(g_stream, launch_arithmetic(a));
+    HIP_TRY(g_stream, hipMemcpyAsync(h, dv + o_gl, tail, hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
     const double* gl = reinterpret_cast<const double*>(h);
     const int32_t* gi = reinterpret_cast<const int32_t*>(h + (o_gi - o_gl));
     const int32_t* gq = reinterpret_cast<const int32_t*>(h + (o_gq - o_gl));
@@ -250,125 +223,79 @@ bool parse_cigar(const char* t, int32_t begin, std::vector<PlanRun>& runs, int32
     return true;
 }
 
-char* g_dev2 = nullptr;   // buffers sized by the site count
-size_t g_dev2_bytes = 0;
-
-int reserve_sites(size_t dev)
-{
-    if (dev <= g_dev2_bytes) return HC_PHMM_OK;
-    if (g_dev2) (void)hipFree(g_dev2);
-    g_dev2 = nullptr;
-    g_dev2_bytes = 0;
-    if (hipMalloc(&g_dev2, dev + dev / 4) != hipSuccess) return fail(HC_PHMM_ENOMEM, "genotyper site workspace");
-    g_dev2_bytes = dev + dev / 4;
-    return HC_PHMM_OK;
-}
-
 int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
 {
     std::vector<PlanRegion> pr(static_cast<size_t>(n));
     std::vector<PlanHap> ph;
     std::vector<PlanRun> runs;
     std::string hap_pool;
-    int64_t ref_total = 0, read_total = 0, L_total = 0, tab_total = 0, keep_bound = 0, map_bound = 0, site_bound = 0;
+    hcgt_host::FrameTotals t;
     for (int32_t r = 0; r < n; ++r) {
         const hc_gt_region& x = regions[r];
-        const std::string at = "region " + std::to_string(r);
-        if (int rc = hcgt_host::check_region_frame(
-                at, !x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.L)), x.ref_len, x.n_haps,
-                x.n_reads, x.padded_begin, x.origin_begin, x.origin_end))
-            return rc;
-        PlanRegion& d = pr[size_t(r)];
-        d.padded_begin = x.padded_begin;
-        d.origin_begin = x.origin_begin;
-        d.origin_end = x.origin_end;
-        d.L_off = L_total;
-        d.ref_off = int32_t(ref_total);
-        d.ref_len = x.ref_len;
-        d.hap0 = int32_t(ph.size());
-        d.n_haps = x.n_haps;
-        d.read_off = int32_t(read_total);
-        d.n_reads = x.n_reads;
-        for (int32_t h = 0; h < x.n_haps; ++h) {
-            const hc_gt_hap_aln& y = x.haps[h];
-            const std::string hat = at + " haplotype " + std::to_string(h);
-            if (int rc = hcgt_host::check_hap_frame(hat, !y.bases || !y.cigar, y.length, y.alignment_begin, x.ref_len))
-                return rc;
-            PlanHap e;
-            e.region = r;
-            e.base_off = int32_t(hap_pool.size());
-            e.run_off = int32_t(runs.size());
-            e.tab_off = int32_t(tab_total);
-            if (int rc = hcgt_host::parse_hap_cigar(hat, y.cigar, y.alignment_begin, y.length, x.ref_len, runs)) return rc;
-            e.n_runs = int32_t(runs.size()) - e.run_off;
-            hap_pool.append(reinterpret_cast<const char*>(y.bases), size_t(y.length));
-            ph.push_back(e);
-            tab_total += x.ref_len;
-        }
-        const int64_t width = std::min<int64_t>(x.origin_end - x.origin_begin, x.ref_len);
-        ref_total += x.ref_len;
-        read_total += x.n_reads;
-        L_total += int64_t(x.n_reads) * x.n_haps;
-        site_bound += width;
-        keep_bound += width * x.n_reads;
-        map_bound += width * x.n_haps;
-        if (tab_total > INT32_MAX || hap_pool.size() > size_t(INT32_MAX) || runs.size() > size_t(INT32_MAX) ||
-            read_total > INT32_MAX || site_bound * kMaxGenotypes > INT32_MAX || keep_bound > INT32_MAX ||
-            map_bound > INT32_MAX)
-            return fail(HC_PHMM_EINVAL, "too many regions for one call");
+        const hcgt_host::RegionFrame f{!x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.L)),
+                                       x.ref_len, x.n_haps, x.n_reads, x.padded_begin, x.origin_begin, x.origin_end};
+        auto haps = [&](const std::string& at) {
+            for (int32_t h = 0; h < x.n_haps; ++h) {
+                const hc_gt_hap_aln& y = x.haps[h];
+                const std::string hat = at + " haplotype " + std::to_string(h);
+                if (int rc = hcgt_host::check_hap_frame(hat, !y.bases || !y.cigar, y.length, y.alignment_begin, x.ref_len))
+                    return rc;
+                PlanHap e;
+                e.region = r;
+                e.base_off = int32_t(hap_pool.size());
+                e.run_off = int32_t(runs.size());
+                e.tab_off = int32_t(t.tab + int64_t(h) * x.ref_len);
+                if (int rc = hcgt_host::parse_hap_cigar(hat, y.cigar, y.alignment_begin, y.length, x.ref_len, runs)) return rc;
+                e.n_runs = int32_t(runs.size()) - e.run_off;
+                hap_pool.append(reinterpret_cast<const char*>(y.bases), size_t(y.length));
+                ph.push_back(e);
+            }
+            return HC_PHMM_OK;
+        };
+        if (int rc = hcgt_host::add_region(r, f, t, pr[size_t(r)], haps, ph, hap_pool, runs)) return rc;
     }
     // Workspace 1: [regions | haps | runs | ref | hap | read_begin | read_end | L] uploaded, then
     // [bitmap | base | totals | ev | span] written by the events and scan kernels.
     const size_t nh = ph.size();
-    const size_t o_reg = 0;
-    const size_t o_hap = up(o_reg + sizeof(PlanRegion) * size_t(n));
-    const size_t o_run = up(o_hap + sizeof(PlanHap) * nh);
-    const size_t o_ref = up(o_run + sizeof(PlanRun) * runs.size());
-    const size_t o_pool = up(o_ref + size_t(ref_total));
-    const size_t o_rb = up(o_pool + hap_pool.size());
-    const size_t o_re = up(o_rb + sizeof(int64_t) * size_t(read_total));
-    const size_t o_L = up(o_re + sizeof(int64_t) * size_t(read_total));
-    const size_t in_bytes = up(o_L + sizeof(double) * size_t(L_total));
-    const size_t o_bm = in_bytes;
-    const size_t o_base = up(o_bm + sizeof(uint32_t) * kBitmapWords * size_t(n));
-    const size_t o_tot = up(o_base + sizeof(PlanBase) * size_t(n));
-    const size_t o_ev = up(o_tot + sizeof(PlanTotals));
-    const size_t o_span = up(o_ev + sizeof(int16_t) * size_t(tab_total));
-    const size_t dev_bytes = up(o_span + sizeof(int16_t) * size_t(tab_total));
+    Carver cv;
+    hcgt_host::PlanOffsets o{};
+    o.reg = cv.take(sizeof(PlanRegion) * size_t(n));
+    o.hap = cv.take(sizeof(PlanHap) * nh);
+    o.runs = cv.take(sizeof(PlanRun) * runs.size());
+    o.ref = cv.take(size_t(t.ref));
+    o.pool = cv.take(hap_pool.size());
+    o.read_begin = cv.take(sizeof(int64_t) * size_t(t.reads));
+    o.read_end = cv.take(sizeof(int64_t) * size_t(t.reads));
+    const size_t o_L = cv.take(sizeof(double) * size_t(t.L));
+    const size_t in_bytes = cv.off;
+    o.bitmap = cv.take(sizeof(uint32_t) * kBitmapWords * size_t(n));
+    o.base = cv.take(sizeof(PlanBase) * size_t(n));
+    o.totals = cv.take(sizeof(PlanTotals));
+    o.ev = cv.take(sizeof(int16_t) * size_t(t.tab));
+    o.span = cv.take(sizeof(int16_t) * size_t(t.tab));
     const size_t h_tot = in_bytes;   // the totals land behind the staged input
-    int rc = reserve(dev_bytes, in_bytes + 256);
+    int rc = reserve(g_dev, cv.off, "genotyper device workspace");
     if (rc) return rc;
-    char* h = g_host;
-    std::memcpy(h + o_reg, pr.data(), sizeof(PlanRegion) * size_t(n));
-    std::memcpy(h + o_hap, ph.data(), sizeof(PlanHap) * nh);
-    std::memcpy(h + o_run, runs.data(), sizeof(PlanRun) * runs.size());
-    std::memcpy(h + o_pool, hap_pool.data(), hap_pool.size());
+    rc = reserve(g_host, in_bytes + 256, "genotyper pinned workspace");
+    if (rc) return rc;
+    char* h = g_host.p;
+    char* const dv = g_dev.p;
+    std::memcpy(h + o.reg, pr.data(), sizeof(PlanRegion) * size_t(n));
+    std::memcpy(h + o.hap, ph.data(), sizeof(PlanHap) * nh);
+    std::memcpy(h + o.runs, runs.data(), sizeof(PlanRun) * runs.size());
+    std::memcpy(h + o.pool, hap_pool.data(), hap_pool.size());
     for (int32_t r = 0; r < n; ++r) {
         const hc_gt_region& x = regions[r];
-        std::memcpy(h + o_ref + size_t(pr[size_t(r)].ref_off), x.ref, size_t(x.ref_len));
+        std::memcpy(h + o.ref + size_t(pr[size_t(r)].ref_off), x.ref, size_t(x.ref_len));
         if (x.n_reads) {
-            std::memcpy(h + o_rb + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_begin, sizeof(int64_t) * size_t(x.n_reads));
-            std::memcpy(h + o_re + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_end, sizeof(int64_t) * size_t(x.n_reads));
+            std::memcpy(h + o.read_begin + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_begin, sizeof(int64_t) * size_t(x.n_reads));
+            std::memcpy(h + o.read_end + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_end, sizeof(int64_t) * size_t(x.n_reads));
         }
     }
-    HIP_TRY(hipMemcpyAsync(g_dev, h, o_L, hipMemcpyHostToDevice, g_stream));
-    PlanArgs p{};
-    p.regions = reinterpret_cast<const PlanRegion*>(g_dev + o_reg);
-    p.n_regions = n;
-    p.haps = reinterpret_cast<const PlanHap*>(g_dev + o_hap);
-    p.n_haps = int(nh);
-    p.runs = reinterpret_cast<const PlanRun*>(g_dev + o_run);
-    p.ref = reinterpret_cast<const uint8_t*>(g_dev + o_ref);
-    p.hap = reinterpret_cast<const uint8_t*>(g_dev + o_pool);
-    p.read_begin = reinterpret_cast<const int64_t*>(g_dev + o_rb);
-    p.read_end = reinterpret_cast<const int64_t*>(g_dev + o_re);
-    p.ev = reinterpret_cast<int16_t*>(g_dev + o_ev);
-    p.span = reinterpret_cast<int16_t*>(g_dev + o_span);
-    p.bitmap = reinterpret_cast<uint32_t*>(g_dev + o_bm);
-    p.base = reinterpret_cast<PlanBase*>(g_dev + o_base);
-    p.totals = reinterpret_cast<PlanTotals*>(g_dev + o_tot);
-    HIP_TRY(launch_plan_events(p, g_stream));
-    HIP_TRY(hipMemcpyAsync(h + h_tot, g_dev + o_tot, sizeof(PlanTotals), hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(g_stream, hipMemcpyAsync(dv, h, o_L, hipMemcpyHostToDevice, g_stream));
+    PlanArgs p = hcgt_host::plan_args(dv, o, n, nh);
+    HIP_TRY(g_stream, launch_plan_events(p, g_stream));
+    HIP_TRY(g_stream, hipMemcpyAsync(h + h_tot, dv + o.totals, sizeof(PlanTotals), hipMemcpyDeviceToHost, g_stream));
     // The matrices are staged while the events and scan kernels run.
     hcphmm::parallel_for(n, [&](int64_t lo, int64_t hi) {
         for (int64_t r = lo; r < hi; ++r) {
@@ -378,49 +305,44 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
                             sizeof(double) * size_t(x.n_reads) * size_t(x.n_haps));
         }
     }, 1);
-    if (in_bytes > o_L) HIP_TRY(hipMemcpyAsync(g_dev + o_L, h + o_L, in_bytes - o_L, hipMemcpyHostToDevice, g_stream));
+    if (t.L) HIP_TRY(g_stream, hipMemcpyAsync(dv + o_L, h + o_L, in_bytes - o_L, hipMemcpyHostToDevice, g_stream));
     // The one counted readback: the site count sizes everything that follows.
-    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
     PlanTotals tot;
     std::memcpy(&tot, h + h_tot, sizeof(tot));
     const int64_t ns = tot.n_sites;
-    if (ns < 0 || ns > site_bound || tot.keep_cap > keep_bound || tot.map_cap > map_bound)
+    if (ns < 0 || ns > t.site_bound || tot.keep_cap > t.keep_bound || tot.map_cap > t.map_bound)
         return fail(HC_PHMM_EHIP, "genotyper site count out of its bound");
     if (ns == 0) return HC_PHMM_OK;
-    // Workspace 2: [site_out | gl | gi | gq | keep | amap] read back, then [gt_sites | al] scratch.
-    const size_t o_so = 0;
-    const size_t o_gl = up(o_so + sizeof(SiteOut) * size_t(ns));
-    const size_t o_gi = up(o_gl + sizeof(double) * kMaxGenotypes * size_t(ns));
-    const size_t o_gq = up(o_gi + sizeof(int32_t) * size_t(ns));
-    const size_t o_keep = up(o_gq + sizeof(int32_t) * size_t(ns));
+    // Workspace 2: [site_out | gl | gi | gq | keep, amap] read back, then [gt_sites | al] scratch.
+    // keep and amap are one piece, the map directly behind the keep list: materialise gets them as one block.
+    Carver c2;
+    const size_t o_so = c2.take(sizeof(SiteOut) * size_t(ns));
+    const size_t o_gl = c2.take(sizeof(double) * kMaxGenotypes * size_t(ns));
+    const size_t o_gi = c2.take(sizeof(int32_t) * size_t(ns));
+    const size_t o_gq = c2.take(sizeof(int32_t) * size_t(ns));
+    const size_t o_keep = c2.take(sizeof(int32_t) * size_t(tot.keep_cap + tot.map_cap));
     const size_t o_map = o_keep + sizeof(int32_t) * size_t(tot.keep_cap);
-    const size_t back = up(o_map + sizeof(int32_t) * size_t(tot.map_cap));
-    const size_t o_gs = back;
-    const size_t o_al = up(o_gs + sizeof(GtSite) * size_t(ns));
-    const size_t dev2_bytes = up(o_al + sizeof(double) * kMaxAlleles * size_t(std::max<int64_t>(tot.keep_cap, 1)));
-    rc = reserve_sites(dev2_bytes);
+    const size_t back = c2.off;
+    const size_t o_gs = c2.take(sizeof(GtSite) * size_t(ns));
+    const size_t o_al = c2.take(sizeof(double) * kMaxAlleles * size_t(tot.keep_cap));
+    rc = reserve(g_dev2, c2.off, "genotyper site workspace");
     if (rc) return rc;
-    rc = reserve(0, back);
+    rc = reserve(g_host, back, "genotyper pinned workspace");
     if (rc) return rc;
-    h = g_host;
-    p.site_out = reinterpret_cast<SiteOut*>(g_dev2 + o_so);
-    p.gt_sites = reinterpret_cast<GtSite*>(g_dev2 + o_gs);
-    p.keep = reinterpret_cast<int32_t*>(g_dev2 + o_keep);
-    p.amap = reinterpret_cast<int32_t*>(g_dev2 + o_map);
-    HIP_TRY(launch_plan_sites(p, ns, g_stream));
-    GtArgs a{};
-    a.sites = p.gt_sites;
-    a.n = int(ns);
-    a.L = reinterpret_cast<const double*>(g_dev + o_L);
-    a.keep = p.keep;
-    a.amap = p.amap;
-    a.al = reinterpret_cast<double*>(g_dev2 + o_al);
-    a.gl = reinterpret_cast<double*>(g_dev2 + o_gl);
-    a.gi = reinterpret_cast<int32_t*>(g_dev2 + o_gi);
-    a.gq = reinterpret_cast<int32_t*>(g_dev2 + o_gq);
-    HIP_TRY(launch_arithmetic(a));
-    HIP_TRY(hipMemcpyAsync(h, g_dev2, back, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
+    h = g_host.p;
+    char* const d2 = g_dev2.p;
+    p.site_out = reinterpret_cast<SiteOut*>(d2 + o_so);
+    p.gt_sites = reinterpret_cast<GtSite*>(d2 + o_gs);
+    p.keep = reinterpret_cast<int32_t*>(d2 + o_keep);
+    p.amap = reinterpret_cast<int32_t*>(d2 + o_map);
+    HIP_TRY(g_stream, launch_plan_sites(p, ns, g_stream));
+    GtArgs a = hcgt_host::gt_args(p, ns, reinterpret_cast<const double*>(dv + o_L), reinterpret_cast<double*>(d2 + o_al),
+                                  reinterpret_cast<double*>(d2 + o_gl), reinterpret_cast<int32_t*>(d2 + o_gi),
+                                  reinterpret_cast<int32_t*>(d2 + o_gq));
+    HIP_TRY(g_stream, launch_arithmetic(a));
+    HIP_TRY(g_stream, hipMemcpyAsync(h, d2, back, hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
     std::vector<RegionView> views(static_cast<size_t>(n));
     for (int32_t r = 0; r < n; ++r) views[size_t(r)] = RegionView{regions[r].ref, regions[r].padded_begin, regions[r].n_haps};
     hcgt_host::materialise(views.data(), hap_pool.data(), reinterpret_cast<const SiteOut*>(h + o_so), ns,
@@ -439,15 +361,76 @@ int ensure_init() { return ::ensure_init(); }
 hipStream_t stream() { return g_stream; }
 hipError_t launch_arithmetic(hcgt::GtArgs& a) { return ::launch_arithmetic(a); }
 
-int check_region_frame(const std::string& at, bool null_pointer, int32_t ref_len, int32_t n_haps, int32_t n_reads,
-                       int64_t padded_begin, int64_t origin_begin, int64_t origin_end)
+int add_region(int32_t r, const RegionFrame& f, FrameTotals& t, PlanRegion& d,
+               const std::function<int(const std::string& at)>& haps, const std::vector<PlanHap>& ph,
+               const std::string& hap_pool, const std::vector<PlanRun>& runs)
 {
-    if (null_pointer) return fail(HC_PHMM_EINVAL, at + ": null pointer");
-    if (ref_len < 1 || ref_len > HC_GT_MAX_REF_LEN || n_haps < 1 || n_haps > HC_GT_MAX_HAPS || n_reads < 0)
+    const std::string at = "region " + std::to_string(r);
+    if (f.null_pointer) return fail(HC_PHMM_EINVAL, at + ": null pointer");
+    if (f.ref_len < 1 || f.ref_len > HC_GT_MAX_REF_LEN || f.n_haps < 1 || f.n_haps > HC_GT_MAX_HAPS || f.n_reads < 0)
         return fail(HC_PHMM_EINVAL, at + ": ref_len, n_haps or n_reads out of range");
-    if (padded_begin < 0 || origin_begin < padded_begin || origin_end < origin_begin || origin_end > padded_begin + ref_len)
+    if (f.padded_begin < 0 || f.origin_begin < f.padded_begin || f.origin_end < f.origin_begin ||
+        f.origin_end > f.padded_begin + f.ref_len)
         return fail(HC_PHMM_EINVAL, at + ": origin outside the padded window");
+    d.padded_begin = f.padded_begin;
+    d.origin_begin = f.origin_begin;
+    d.origin_end = f.origin_end;
+    d.L_off = t.L;
+    d.ref_off = int32_t(t.ref);
+    d.ref_len = f.ref_len;
+    d.hap0 = int32_t(ph.size());
+    d.n_haps = f.n_haps;
+    d.read_off = int32_t(t.reads);
+    d.n_reads = f.n_reads;
+    if (int rc = haps(at)) return rc;
+    const int64_t width = std::min<int64_t>(f.origin_end - f.origin_begin, f.ref_len);
+    t.ref += f.ref_len;
+    t.reads += f.n_reads;
+    t.L += int64_t(f.n_reads) * f.n_haps;
+    t.tab += int64_t(f.n_haps) * f.ref_len;
+    t.site_bound += width;
+    t.keep_bound += width * f.n_reads;   // by the unfiltered count: a scan may run before a filter
+    t.map_bound += width * f.n_haps;
+    if (t.tab > INT32_MAX || hap_pool.size() > size_t(INT32_MAX) || runs.size() > size_t(INT32_MAX) ||
+        t.reads > INT32_MAX || t.site_bound * kMaxGenotypes > INT32_MAX || t.keep_bound > INT32_MAX ||
+        t.map_bound > INT32_MAX)
+        return fail(HC_PHMM_EINVAL, "too many regions for one call");
     return HC_PHMM_OK;
+}
+
+PlanArgs plan_args(char* base, const PlanOffsets& o, int32_t n_regions, size_t n_haps)
+{
+    PlanArgs p{};
+    p.regions = reinterpret_cast<const PlanRegion*>(base + o.reg);
+    p.n_regions = n_regions;
+    p.haps = reinterpret_cast<const PlanHap*>(base + o.hap);
+    p.n_haps = int(n_haps);
+    p.runs = reinterpret_cast<const PlanRun*>(base + o.runs);
+    p.ref = reinterpret_cast<const uint8_t*>(base + o.ref);
+    p.hap = reinterpret_cast<const uint8_t*>(base + o.pool);
+    p.read_begin = reinterpret_cast<const int64_t*>(base + o.read_begin);
+    p.read_end = reinterpret_cast<const int64_t*>(base + o.read_end);
+    p.ev = reinterpret_cast<int16_t*>(base + o.ev);
+    p.span = reinterpret_cast<int16_t*>(base + o.span);
+    p.bitmap = reinterpret_cast<uint32_t*>(base + o.bitmap);
+    p.base = reinterpret_cast<PlanBase*>(base + o.base);
+    p.totals = reinterpret_cast<PlanTotals*>(base + o.totals);
+    return p;
+}
+
+GtArgs gt_args(const PlanArgs& p, int64_t n_sites, const double* L, double* al, double* gl, int32_t* gi, int32_t* gq)
+{
+    GtArgs a{};
+    a.sites = p.gt_sites;
+    a.n = int(n_sites);
+    a.L = L;
+    a.keep = p.keep;
+    a.amap = p.amap;
+    a.al = al;
+    a.gl = gl;
+    a.gi = gi;
+    a.gq = gq;
+    return a;
 }
 
 int check_hap_frame(const std::string& hat, bool null_pointer, int32_t length, int32_t alignment_begin, int32_t ref_len)
@@ -614,15 +597,8 @@ void hcphmm::gt_release()
     if (!g_stream) return;
     (void)hipStreamSynchronize(g_stream);
     if (g_jac) (void)hipFree(g_jac);
-    if (g_dev) (void)hipFree(g_dev);
-    if (g_dev2) (void)hipFree(g_dev2);
-    g_dev2 = nullptr;
-    g_dev2_bytes = 0;
-    if (g_host) (void)hipHostFree(g_host);
+    g_jac = nullptr;
+    for (Buf* b : {&g_dev, &g_dev2, &g_host}) drop(*b);
     (void)hipStreamDestroy(g_stream);
     g_stream = nullptr;
-    g_jac = nullptr;
-    g_dev = nullptr;
-    g_host = nullptr;
-    g_dev_bytes = g_host_bytes = 0;
 }

@@ -15,15 +15,17 @@
 //   one readback: records, likelihoods, maps, keep bytes and counts, and only
 //     on request the per-site read lists, the matrices and the CIGAR elements
 //
-// The workspace is the call's own (grow-only, released by hc_phmm_shutdown);
-// stream, lock and Jacobian table are the genotyper's, so the call serialises
-// with hc_gt_* as those do among themselves.
+// The workspace is the call's own: four grow-only buffers of the shared host
+// layer (stage_host.hpp), released by hc_phmm_shutdown ahead of the genotyper's.
+// Stream, lock and Jacobian table are the genotyper's, so the call serialises
+// with hc_gt_* as those do among themselves; the frame of a region and the
+// PlanArgs / GtArgs helpers are the genotyper's too (gt_engine_internal.hpp).
+// Inside a call HIP_BAIL wraps the shared HIP error text: collect the PairHMM
+// job, drain the stream, restore the message.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -33,10 +35,10 @@
 #include "gt_engine_internal.hpp"
 #include "pool.hpp"
 #include "region_kernels.hpp"
+#include "stage_host.hpp"
 #include "sw_engine_internal.hpp"
 
 namespace hcphmm {
-void set_last_error(const std::string& msg);
 void region_release();
 int submit_regions_with_mode(const hc_phmm_region* regions, int32_t n_regions, uint32_t mode, hc_phmm_job** job);
 uint32_t default_mode();
@@ -44,89 +46,12 @@ uint32_t default_mode();
 
 using namespace hcgt;
 using namespace hcregion;
+using namespace stage_host;
 
 namespace {
 
 // Grow-only buffers, guarded by the genotyper's lock.
-struct Buf {
-    char* p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-};
 Buf g_dev1, g_dev2, g_hin{nullptr, 0, true}, g_hback{nullptr, 0, true};
-
-int fail(int code, const std::string& msg)
-{
-    hcphmm::set_last_error(msg);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(HC_PHMM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-void drop(Buf& b)
-{
-    if (b.p) (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-int reserve(Buf& b, size_t bytes, const char* what)
-{
-    if (bytes <= b.bytes) return HC_PHMM_OK;
-    drop(b);
-    const size_t want = bytes + bytes / 4;
-    const hipError_t e = b.pinned ? hipHostMalloc(reinterpret_cast<void**>(&b.p), want, hipHostMallocDefault)
-                                  : hipMalloc(reinterpret_cast<void**>(&b.p), want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return fail(HC_PHMM_ENOMEM, std::string("region caller ") + what);
-    }
-    b.bytes = want;
-    return HC_PHMM_OK;
-}
-
-size_t up(size_t x) { return (x + 255) & ~size_t(255); }
-
-// Carves consecutive 256-byte aligned pieces.
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t at = off;
-        off = up(off + std::max<size_t>(bytes, 1));
-        return at;
-    }
-};
-
-// HC_REGION_TRACE=1: host wall clock of a call's phases on stderr (ms since the call began).
-struct Trace {
-    bool on = false;
-    std::chrono::steady_clock::time_point t0;
-    std::string line;
-    Trace()
-    {
-        const char* e = std::getenv("HC_REGION_TRACE");
-        on = e && e[0] == '1';
-        if (on) t0 = std::chrono::steady_clock::now();
-    }
-    void mark(const char* what)
-    {
-        if (!on) return;
-        char tmp[64];
-        std::snprintf(tmp, sizeof(tmp), " %s=%.3f", what,
-                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        line += tmp;
-    }
-    ~Trace()
-    {
-        if (on) std::fprintf(stderr, "[hc_region]%s\n", line.c_str());
-    }
-};
 
 // The aligner as hc::MI355XSWAligner::align_haplotypes runs it.
 constexpr hc_sw_params kSwParams{200, -150, -260, -11};   // NEW_SW_PARAMETERS
@@ -172,7 +97,7 @@ namespace {
 int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls& out)
 {
     const hipStream_t st = hcgt_host::stream();
-    Trace trace;
+    Trace trace("HC_REGION_TRACE", "[hc_region]");
     // ---- validate and lay out
     std::vector<PlanRegion> pr(static_cast<size_t>(n));
     std::vector<PlanHap> ph;
@@ -183,72 +108,52 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
     std::vector<hc_phmm_region> hr(static_cast<size_t>(n));
     std::string hap_pool;
     out.aligned.assign(size_t(n), 0);
-    int64_t ref_total = 0, read_total = 0, L_total = 0, tab_total = 0, keep_bound = 0, map_bound = 0, site_bound = 0;
+    hcgt_host::FrameTotals t;
     for (int32_t r = 0; r < n; ++r) {
         const hc_region_in& x = regions[r];
-        const std::string at = "region " + std::to_string(r);
-        if (int rc = hcgt_host::check_region_frame(
-                at, !x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.reads)), x.ref_len,
-                x.n_haps, x.n_reads, x.padded_begin, x.origin_begin, x.origin_end))
-            return rc;
-        int with = 0;
-        for (int32_t h = 0; h < x.n_haps; ++h) with += x.haps[h].cigar != nullptr;
-        if (with != 0 && with != x.n_haps)
-            return fail(HC_PHMM_EINVAL, at + ": haplotypes with and without a CIGAR (all or none)");
-        out.aligned[size_t(r)] = with == 0;
+        const hcgt_host::RegionFrame f{!x.ref || !x.haps || (x.n_reads > 0 && (!x.read_begin || !x.read_end || !x.reads)),
+                                       x.ref_len, x.n_haps, x.n_reads, x.padded_begin, x.origin_begin, x.origin_end};
         PlanRegion& d = pr[size_t(r)];
-        d.padded_begin = x.padded_begin;
-        d.origin_begin = x.origin_begin;
-        d.origin_end = x.origin_end;
-        d.L_off = L_total;
-        d.ref_off = int32_t(ref_total);
-        d.ref_len = x.ref_len;
-        d.hap0 = int32_t(ph.size());
-        d.n_haps = x.n_haps;
-        d.read_off = int32_t(read_total);
-        d.n_reads = x.n_reads;
-        for (int32_t h = 0; h < x.n_haps; ++h) {
-            const hc_region_hap& y = x.haps[h];
-            const std::string hat = at + " haplotype " + std::to_string(h);
-            if (int rc = hcgt_host::check_hap_frame(hat, !y.bases, y.length, y.cigar ? y.alignment_begin : 0, x.ref_len))
-                return rc;
-            PlanHap e;
-            e.region = r;
-            e.base_off = int32_t(hap_pool.size());
-            e.tab_off = int32_t(tab_total);
-            e.run_off = 0;   // device-aligned: written by region_runs_kernel
-            e.n_runs = 0;
-            if (y.cigar) {
-                e.run_off = int32_t(host_runs.size());   // rebased behind the device runs below
-                if (int rc = hcgt_host::parse_hap_cigar(hat, y.cigar, y.alignment_begin, y.length, x.ref_len, host_runs))
+        auto haps = [&](const std::string& at) {
+            int with = 0;
+            for (int32_t h = 0; h < x.n_haps; ++h) with += x.haps[h].cigar != nullptr;
+            if (with != 0 && with != x.n_haps)
+                return fail(HC_PHMM_EINVAL, at + ": haplotypes with and without a CIGAR (all or none)");
+            out.aligned[size_t(r)] = with == 0;
+            for (int32_t h = 0; h < x.n_haps; ++h) {
+                const hc_region_hap& y = x.haps[h];
+                const std::string hat = at + " haplotype " + std::to_string(h);
+                if (int rc = hcgt_host::check_hap_frame(hat, !y.bases, y.length, y.cigar ? y.alignment_begin : 0, x.ref_len))
                     return rc;
-                e.n_runs = int32_t(host_runs.size()) - e.run_off;
-            } else {
-                hcsw::SwPair P{};
-                P.ref_off = d.ref_off;
-                P.alt_off = e.base_off;
-                P.n1 = x.ref_len;
-                P.n2 = y.length;
-                pairs.push_back(P);
-                pair_hap.push_back(int32_t(ph.size()));
+                PlanHap e;
+                e.region = r;
+                e.base_off = int32_t(hap_pool.size());
+                e.tab_off = int32_t(t.tab + int64_t(h) * x.ref_len);
+                e.run_off = 0;   // device-aligned: written by region_runs_kernel
+                e.n_runs = 0;
+                if (y.cigar) {
+                    e.run_off = int32_t(host_runs.size());   // rebased behind the device runs below
+                    if (int rc = hcgt_host::parse_hap_cigar(hat, y.cigar, y.alignment_begin, y.length, x.ref_len, host_runs))
+                        return rc;
+                    e.n_runs = int32_t(host_runs.size()) - e.run_off;
+                } else {
+                    hcsw::SwPair P{};
+                    P.ref_off = d.ref_off;
+                    P.alt_off = e.base_off;
+                    P.n1 = x.ref_len;
+                    P.n2 = y.length;
+                    pairs.push_back(P);
+                    pair_hap.push_back(int32_t(ph.size()));
+                }
+                hap_pool.append(reinterpret_cast<const char*>(y.bases), size_t(y.length));
+                hh.push_back(hc_phmm_hap{y.length, reinterpret_cast<const char*>(y.bases)});
+                ph.push_back(e);
             }
-            hap_pool.append(reinterpret_cast<const char*>(y.bases), size_t(y.length));
-            hh.push_back(hc_phmm_hap{y.length, reinterpret_cast<const char*>(y.bases)});
-            ph.push_back(e);
-            tab_total += x.ref_len;
-        }
-        const int64_t width = std::min<int64_t>(x.origin_end - x.origin_begin, x.ref_len);
-        ref_total += x.ref_len;
-        read_total += x.n_reads;
-        L_total += int64_t(x.n_reads) * x.n_haps;
-        site_bound += width;
-        keep_bound += width * x.n_reads;   // by the unfiltered count: the scan runs before the filter
-        map_bound += width * x.n_haps;
-        if (tab_total > INT32_MAX || hap_pool.size() > size_t(INT32_MAX) || host_runs.size() > size_t(INT32_MAX) ||
-            read_total > INT32_MAX || site_bound * kMaxGenotypes > INT32_MAX || keep_bound > INT32_MAX ||
-            map_bound > INT32_MAX)
-            return fail(HC_PHMM_EINVAL, "too many regions for one call");
+            return HC_PHMM_OK;
+        };
+        if (int rc = hcgt_host::add_region(r, f, t, d, haps, ph, hap_pool, host_runs)) return rc;
     }
+    const int64_t read_total = t.reads, L_total = t.L;
     const size_t nh = ph.size(), np = pairs.size();
     const hcsw_host::PairLayout lay = hcsw_host::layout_pairs(pairs);
     // Run buffer: the aligner's own bound of n1 + n2 + 3 elements per pair, at the
@@ -262,13 +167,14 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
     //   uploaded [regions | haps | pairs | order | pair_hap | ref | hap | host runs]
     //   device   [res | bt | elems | slots | n_elems | offsets | runs | bitmap | base | totals + err | ev | span]
     Carver cv;
-    const size_t o_reg = cv.take(sizeof(PlanRegion) * size_t(n));
-    const size_t o_hap = cv.take(sizeof(PlanHap) * nh);
+    hcgt_host::PlanOffsets o{};
+    o.reg = cv.take(sizeof(PlanRegion) * size_t(n));
+    o.hap = cv.take(sizeof(PlanHap) * nh);
     const size_t o_pairs = cv.take(sizeof(hcsw::SwPair) * np);
     const size_t o_order = cv.take(sizeof(int32_t) * np);
     const size_t o_phap = cv.take(sizeof(int32_t) * np);
-    const size_t o_ref = cv.take(size_t(ref_total));
-    const size_t o_pool = cv.take(hap_pool.size());
+    o.ref = cv.take(size_t(t.ref));
+    o.pool = cv.take(hap_pool.size());
     const size_t o_hruns = cv.take(sizeof(PlanRun) * host_runs.size());
     const size_t a_in = cv.off;
     const size_t o_res = cv.take(sizeof(hcsw::SwResult) * np);
@@ -278,16 +184,18 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
     const size_t o_nel = cv.take(sizeof(int32_t) * np);
     const size_t o_offs = cv.take(sizeof(int32_t) * np);
     const size_t sw_tail = cv.off - o_slots;   // [slots | n_elems | offsets]
-    const size_t o_runs = cv.take(sizeof(PlanRun) * size_t(run_total));
-    const size_t o_bm = cv.take(sizeof(uint32_t) * kBitmapWords * size_t(n));
-    const size_t o_base = cv.take(sizeof(PlanBase) * size_t(n));
-    const size_t o_tot = cv.take(sizeof(PlanTotals) + sizeof(uint32_t));   // the error word sits behind the totals
-    const size_t o_err = o_tot + sizeof(PlanTotals);
-    const size_t o_ev = cv.take(sizeof(int16_t) * size_t(tab_total));
-    const size_t o_span = cv.take(sizeof(int16_t) * size_t(tab_total));
+    o.runs = cv.take(sizeof(PlanRun) * size_t(run_total));
+    o.bitmap = cv.take(sizeof(uint32_t) * kBitmapWords * size_t(n));
+    o.base = cv.take(sizeof(PlanBase) * size_t(n));
+    o.totals = cv.take(sizeof(PlanTotals) + sizeof(uint32_t));   // the error word sits behind the totals
+    const size_t o_err = o.totals + sizeof(PlanTotals);
+    o.ev = cv.take(sizeof(int16_t) * size_t(t.tab));
+    o.span = cv.take(sizeof(int16_t) * size_t(t.tab));
     // part B (after the PairHMM): pinned image = device image shifted by b0
     const size_t b0 = cv.off;
     const FinishLayout fl(cv, read_total, L_total);
+    o.read_begin = fl.o_rbo;   // the compacted intervals
+    o.read_end = fl.o_reo;
     const size_t dev1_bytes = cv.off;
     const size_t b_in = fl.in_end - b0;
     // Pinned input block: [part A inputs | part B inputs | totals + err | aligner tail]
@@ -295,9 +203,9 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
     const size_t h_tot = up(h_b + b_in);
     const size_t h_tail = up(h_tot + sizeof(PlanTotals) + sizeof(uint32_t));
     const bool want_cigars = (flags & HC_REGION_WANT_CIGARS) && np > 0;
-    int rc = reserve(g_dev1, dev1_bytes, "device workspace");
+    int rc = reserve(g_dev1, dev1_bytes, "region caller device workspace");
     if (rc) return rc;
-    rc = reserve(g_hin, h_tail + (want_cigars ? sw_tail : 0), "pinned workspace");
+    rc = reserve(g_hin, h_tail + (want_cigars ? sw_tail : 0), "region caller pinned workspace");
     if (rc) return rc;
     char* const h = g_hin.p;
     char* const dv = g_dev1.p;
@@ -314,29 +222,29 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
         hcphmm::set_last_error(msg);
         return code;
     };
-#define HIP_BAIL(expr)                                                                            \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return bail(fail(HC_PHMM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)));   \
+    // (hip_fail with no stream only sets the message: bail collects, then drains, then restores it)
+#define HIP_BAIL(expr)                                                              \
+    do {                                                                            \
+        hipError_t e_ = (expr);                                                     \
+        if (e_ != hipSuccess) return bail(hip_fail(nullptr, #expr, e_));            \
     } while (0)
 
     // ---- part A, enqueued ahead of the PairHMM job: the device works through it
     // while the host plans and packs that job (a quarter of the call), and the
     // PairHMM kernels then find the device free
-    std::memcpy(h + o_reg, pr.data(), sizeof(PlanRegion) * size_t(n));
-    std::memcpy(h + o_hap, ph.data(), sizeof(PlanHap) * nh);
+    std::memcpy(h + o.reg, pr.data(), sizeof(PlanRegion) * size_t(n));
+    std::memcpy(h + o.hap, ph.data(), sizeof(PlanHap) * nh);
     if (np) {
         std::memcpy(h + o_pairs, pairs.data(), sizeof(hcsw::SwPair) * np);
         std::memcpy(h + o_order, lay.order.data(), sizeof(int32_t) * np);
         std::memcpy(h + o_phap, pair_hap.data(), sizeof(int32_t) * np);
     }
-    std::memcpy(h + o_pool, hap_pool.data(), hap_pool.size());
+    std::memcpy(h + o.pool, hap_pool.data(), hap_pool.size());
     if (!host_runs.empty()) std::memcpy(h + o_hruns, host_runs.data(), sizeof(PlanRun) * host_runs.size());
     for (int32_t r = 0; r < n; ++r)
-        std::memcpy(h + o_ref + size_t(pr[size_t(r)].ref_off), regions[r].ref, size_t(regions[r].ref_len));
+        std::memcpy(h + o.ref + size_t(pr[size_t(r)].ref_off), regions[r].ref, size_t(regions[r].ref_len));
     HIP_BAIL(hipMemcpyAsync(dv, h, a_in, hipMemcpyHostToDevice, st));
-    PlanRun* const d_runs = reinterpret_cast<PlanRun*>(dv + o_runs);
+    PlanRun* const d_runs = reinterpret_cast<PlanRun*>(dv + o.runs);
     if (!host_runs.empty())
         HIP_BAIL(hipMemcpyAsync(d_runs + lay.el_total, dv + o_hruns, sizeof(PlanRun) * host_runs.size(),
                                 hipMemcpyDeviceToDevice, st));
@@ -346,8 +254,8 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
         b.n = int64_t(np);
         b.pairs = reinterpret_cast<const hcsw::SwPair*>(dv + o_pairs);
         b.order = reinterpret_cast<const int32_t*>(dv + o_order);
-        b.refs = reinterpret_cast<const uint8_t*>(dv + o_ref);
-        b.alts = reinterpret_cast<const uint8_t*>(dv + o_pool);
+        b.refs = reinterpret_cast<const uint8_t*>(dv + o.ref);
+        b.alts = reinterpret_cast<const uint8_t*>(dv + o.pool);
         b.res = reinterpret_cast<hcsw::SwResult*>(dv + o_res);
         b.bt = reinterpret_cast<uint32_t*>(dv + o_bt);
         b.elems = reinterpret_cast<uint32_t*>(dv + o_el);
@@ -371,27 +279,13 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
         ra.offsets = b.offsets;
         ra.n = int(np);
         ra.runs = d_runs;
-        ra.haps = reinterpret_cast<PlanHap*>(dv + o_hap);
+        ra.haps = reinterpret_cast<PlanHap*>(dv + o.hap);
         ra.err = reinterpret_cast<uint32_t*>(dv + o_err);
         HIP_BAIL(launch_runs(ra, st));
     }
-    PlanArgs p{};
-    p.regions = reinterpret_cast<const PlanRegion*>(dv + o_reg);
-    p.n_regions = n;
-    p.haps = reinterpret_cast<const PlanHap*>(dv + o_hap);
-    p.n_haps = int(nh);
-    p.runs = d_runs;
-    p.ref = reinterpret_cast<const uint8_t*>(dv + o_ref);
-    p.hap = reinterpret_cast<const uint8_t*>(dv + o_pool);
-    p.read_begin = reinterpret_cast<const int64_t*>(dv + fl.o_rbo);   // the compacted intervals
-    p.read_end = reinterpret_cast<const int64_t*>(dv + fl.o_reo);
-    p.ev = reinterpret_cast<int16_t*>(dv + o_ev);
-    p.span = reinterpret_cast<int16_t*>(dv + o_span);
-    p.bitmap = reinterpret_cast<uint32_t*>(dv + o_bm);
-    p.base = reinterpret_cast<PlanBase*>(dv + o_base);
-    p.totals = reinterpret_cast<PlanTotals*>(dv + o_tot);
+    PlanArgs p = hcgt_host::plan_args(dv, o, n, nh);
     HIP_BAIL(launch_plan_events(p, st));
-    HIP_BAIL(hipMemcpyAsync(h + h_tot, dv + o_tot, sizeof(PlanTotals) + sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_BAIL(hipMemcpyAsync(h + h_tot, dv + o.totals, sizeof(PlanTotals) + sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (want_cigars) HIP_BAIL(hipMemcpyAsync(h + h_tail, dv + o_slots, sw_tail, hipMemcpyDeviceToHost, st));
     // A query makes the runtime hand the queued work to the device now, not at the next wait.
     (void)hipStreamQuery(st);
@@ -433,7 +327,7 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
         return bail(fail(HC_PHMM_EHIP, "region caller: the aligner's CIGAR elements do not form valid runs (error word " +
                                            std::to_string(err) + ")"));
     const int64_t ns = tot.n_sites;
-    if (ns < 0 || ns > site_bound || tot.keep_cap > keep_bound || tot.map_cap > map_bound)
+    if (ns < 0 || ns > t.site_bound || tot.keep_cap > t.keep_bound || tot.map_cap > t.map_bound)
         return bail(fail(HC_PHMM_EHIP, "genotyper site count out of its bound"));
     // CIGAR text of the device-aligned haplotypes, "%d%c" as hc_sw_align_flat prints it.
     if (flags & HC_REGION_WANT_CIGARS) {
@@ -490,15 +384,15 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
     const size_t o_al = c2.take(sizeof(double) * kMaxAlleles * size_t(std::max<int64_t>(tot.keep_cap, 1)));
     const bool want_L = (flags & HC_REGION_WANT_L) != 0;
     const size_t h_L = up(back);
-    rc = reserve(g_dev2, c2.off, "site workspace");
+    rc = reserve(g_dev2, c2.off, "region caller site workspace");
     if (rc) return bail(rc);
-    rc = reserve(g_hback, h_L + (want_L ? sizeof(double) * size_t(L_total) : 0), "pinned readback");
+    rc = reserve(g_hback, h_L + (want_L ? sizeof(double) * size_t(L_total) : 0), "region caller pinned readback");
     if (rc) return bail(rc);
     char* const d2 = g_dev2.p;
     char* const hb = g_hback.p;
     if (b_in) HIP_BAIL(hipMemcpyAsync(dv + b0, h + h_b, b_in, hipMemcpyHostToDevice, st));
     FinishArgs fa{};
-    fa.regions = reinterpret_cast<PlanRegion*>(dv + o_reg);
+    fa.regions = reinterpret_cast<PlanRegion*>(dv + o.reg);
     fa.n_regions = n;
     fa.n_reads = int(read_total);
     fa.read_len = reinterpret_cast<const int32_t*>(dv + fl.o_len);
@@ -518,16 +412,9 @@ int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls&
         p.keep = reinterpret_cast<int32_t*>(d2 + o_keep);
         p.amap = reinterpret_cast<int32_t*>(d2 + o_map);
         HIP_BAIL(launch_plan_sites(p, ns, st));
-        GtArgs a{};
-        a.sites = p.gt_sites;
-        a.n = int(ns);
-        a.L = fa.L_out;
-        a.keep = p.keep;
-        a.amap = p.amap;
-        a.al = reinterpret_cast<double*>(d2 + o_al);
-        a.gl = reinterpret_cast<double*>(d2 + o_gl);
-        a.gi = reinterpret_cast<int32_t*>(d2 + o_gi);
-        a.gq = reinterpret_cast<int32_t*>(d2 + o_gq);
+        GtArgs a = hcgt_host::gt_args(p, ns, fa.L_out, reinterpret_cast<double*>(d2 + o_al),
+                                      reinterpret_cast<double*>(d2 + o_gl), reinterpret_cast<int32_t*>(d2 + o_gi),
+                                      reinterpret_cast<int32_t*>(d2 + o_gq));
         HIP_BAIL(hcgt_host::launch_arithmetic(a));
     }
     // ---- the one readback
@@ -688,9 +575,9 @@ extern "C" int hcx_region_finish(const double* L, int32_t n_regions, const int32
     const FinishLayout fl(cv, reads, L_total);
     const size_t o_keepb = cv.take(size_t(reads));
     const size_t o_nk = cv.take(sizeof(int32_t) * size_t(n_regions));
-    rc = reserve(g_dev1, cv.off, "device workspace");
+    rc = reserve(g_dev1, cv.off, "region caller device workspace");
     if (rc) return rc;
-    rc = reserve(g_hin, fl.in_end, "pinned workspace");
+    rc = reserve(g_hin, fl.in_end, "region caller pinned workspace");
     if (rc) return rc;
     char* const h = g_hin.p;
     char* const dv = g_dev1.p;
@@ -706,7 +593,7 @@ extern "C" int hcx_region_finish(const double* L, int32_t n_regions, const int32
                 re[pr[size_t(r)].read_off + i] = int64_t(i) + 1000;
             }
     }
-    HIP_TRY(hipMemcpyAsync(dv, h, fl.in_end, hipMemcpyHostToDevice, st));
+    HIP_TRY(st, hipMemcpyAsync(dv, h, fl.in_end, hipMemcpyHostToDevice, st));
     FinishArgs fa{};
     fa.regions = reinterpret_cast<PlanRegion*>(dv + o_reg);
     fa.n_regions = n_regions;
@@ -722,16 +609,16 @@ extern "C" int hcx_region_finish(const double* L, int32_t n_regions, const int32
     fa.dest = reinterpret_cast<int32_t*>(dv + fl.o_dest);
     fa.n_kept = reinterpret_cast<int32_t*>(dv + o_nk);
     // The out-of-place matrix starts as zeros here, so the rows behind the kept ones are defined.
-    HIP_TRY(hipMemsetAsync(dv + fl.o_Lout, 0, sizeof(double) * size_t(std::max<int64_t>(L_total, 1)), st));
-    HIP_TRY(hipMemsetAsync(dv + fl.o_rbo, 0xff, sizeof(int64_t) * size_t(std::max<int64_t>(reads, 1)), st));
-    HIP_TRY(launch_finish(fa, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(st, hipMemsetAsync(dv + fl.o_Lout, 0, sizeof(double) * size_t(std::max<int64_t>(L_total, 1)), st));
+    HIP_TRY(st, hipMemsetAsync(dv + fl.o_rbo, 0xff, sizeof(int64_t) * size_t(std::max<int64_t>(reads, 1)), st));
+    HIP_TRY(st, launch_finish(fa, st));
+    HIP_TRY(st, hipStreamSynchronize(st));
     if (reads) {
-        HIP_TRY(hipMemcpy(L_out, dv + fl.o_Lout, sizeof(double) * size_t(L_total), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(keep, dv + o_keepb, size_t(reads), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(order_out, dv + fl.o_rbo, sizeof(int64_t) * size_t(reads), hipMemcpyDeviceToHost));
+        HIP_TRY(st, hipMemcpy(L_out, dv + fl.o_Lout, sizeof(double) * size_t(L_total), hipMemcpyDeviceToHost));
+        HIP_TRY(st, hipMemcpy(keep, dv + o_keepb, size_t(reads), hipMemcpyDeviceToHost));
+        HIP_TRY(st, hipMemcpy(order_out, dv + fl.o_rbo, sizeof(int64_t) * size_t(reads), hipMemcpyDeviceToHost));
     }
-    HIP_TRY(hipMemcpy(n_kept, dv + o_nk, sizeof(int32_t) * size_t(n_regions), hipMemcpyDeviceToHost));
+    HIP_TRY(st, hipMemcpy(n_kept, dv + o_nk, sizeof(int32_t) * size_t(n_regions), hipMemcpyDeviceToHost));
     return HC_PHMM_OK;
 }
 

@@ -8,6 +8,10 @@
 //            (getCIGAR + compaction)                              [device only]
 //   results  D2H offsets + packed CIGAR elements, "%d%c" formatting on the host
 //            (PairWiseSW.h:388-413)
+//
+// hc_sw_align_flat borrows a grow-only workspace: a device and a pinned buffer
+// of the shared host layer (stage_host.hpp) and three events. A batch the caller
+// creates owns its device memory instead. A HIP error drains the stream it names.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,15 +27,16 @@
 #include "../../include/hc_pairhmm.h"
 #include "../../include/hc_sw.h"
 #include "sw_engine_internal.hpp"
+#include "stage_host.hpp"
 #include "sw_kernels.hpp"
 
 namespace hcphmm {
-void set_last_error(const std::string& msg);
 int primary_device();
 void sw_release();
 }
 
 using namespace hcsw;
+using namespace stage_host;
 
 namespace {
 
@@ -41,25 +46,9 @@ hipStream_t g_stream = nullptr;
 // Grow-only workspace of the synchronous entry point (hc_sw_align_flat): a
 // warm call does no hipMalloc / hipHostMalloc and one H2D + one D2H.
 struct Workspace {
-    char* dev = nullptr;
-    size_t dev_bytes = 0;
-    char* host = nullptr;   // pinned
-    size_t host_bytes = 0;
+    Buf dev, host{nullptr, 0, true};
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 } g_ws;
-
-int fail(int code, const std::string& msg)
-{
-    hcphmm::set_last_error(msg);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return fail(HC_SW_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // The aligner runs on the engine's first device slot (hc_phmm_init /
 // hc_phmm_init_devices); every entry point makes that device current on the
@@ -68,12 +57,10 @@ int ensure_init(int device)
 {
     const int rc = hc_phmm_init(0, device);   // device selection + gfx950 check (no-op once initialised)
     if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(hipSetDevice(hcphmm::primary_device()));
-    if (!g_stream) HIP_TRY(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
+    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
+    if (!g_stream) HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
     return HC_SW_OK;
 }
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // The DP kernel's fast variant drops the MATRIX_MIN_CUTOFF max and reads its
 // backtrack bits as signs of differences. Both are exact when every H stays
@@ -154,25 +141,10 @@ void free_batch(hc_sw_batch* b)
 
 int ws_reserve(size_t dev_bytes, size_t host_bytes)
 {
-    if (dev_bytes > g_ws.dev_bytes) {
-        if (g_ws.dev) (void)hipFree(g_ws.dev);
-        g_ws.dev = nullptr;
-        g_ws.dev_bytes = 0;
-        const size_t want = dev_bytes + dev_bytes / 4;
-        if (hipMalloc(&g_ws.dev, want) != hipSuccess) return fail(HC_SW_ENOMEM, "workspace device allocation");
-        g_ws.dev_bytes = want;
-    }
-    if (host_bytes > g_ws.host_bytes) {
-        if (g_ws.host) (void)hipHostFree(g_ws.host);
-        g_ws.host = nullptr;
-        g_ws.host_bytes = 0;
-        const size_t want = host_bytes + host_bytes / 4;
-        if (hipHostMalloc(&g_ws.host, want, hipHostMallocDefault) != hipSuccess)
-            return fail(HC_SW_ENOMEM, "workspace pinned allocation");
-        g_ws.host_bytes = want;
-    }
+    if (int rc = reserve(g_ws.dev, dev_bytes, "workspace device allocation")) return rc;
+    if (int rc = reserve(g_ws.host, host_bytes, "workspace pinned allocation")) return rc;
     for (auto& e : g_ws.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+        if (!e) HIP_TRY(g_stream, hipEventCreate(&e));
     return HC_SW_OK;
 }
 
@@ -234,41 +206,36 @@ int create(int64_t n, const int64_t* ref_off, const int32_t* ref_len, const uint
     b->fast = hcsw_host::dp_variant(params, overhang, b->n1max, b->n2max);
 
     // One device allocation: descriptors, inputs, outputs, scratch.
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + std::max<size_t>(bytes, 1), 256);
-        return at;
-    };
-    const size_t o_pairs = carve(sizeof(SwPair) * size_t(n));
-    const size_t o_order = carve(sizeof(int32_t) * size_t(n));
-    const size_t o_refs = carve(size_t(ref_ext));
-    const size_t o_alts = carve(size_t(alt_ext));
-    const size_t in_bytes = off;
-    const size_t o_res = carve(sizeof(SwResult) * size_t(n));
-    const size_t o_bt = carve(sizeof(uint32_t) * size_t(bt_total));
-    const size_t o_el = carve(sizeof(uint32_t) * size_t(el_total));
-    const size_t o_slots = carve(sizeof(uint16_t) * kSlotElems * size_t(n));
-    const size_t o_nel = carve(sizeof(int32_t) * size_t(n));
-    const size_t o_offs = carve(sizeof(int32_t) * size_t(n));
+    Carver cv;
+    const size_t o_pairs = cv.take(sizeof(SwPair) * size_t(n));
+    const size_t o_order = cv.take(sizeof(int32_t) * size_t(n));
+    const size_t o_refs = cv.take(size_t(ref_ext));
+    const size_t o_alts = cv.take(size_t(alt_ext));
+    const size_t in_bytes = cv.off;
+    const size_t o_res = cv.take(sizeof(SwResult) * size_t(n));
+    const size_t o_bt = cv.take(sizeof(uint32_t) * size_t(bt_total));
+    const size_t o_el = cv.take(sizeof(uint32_t) * size_t(el_total));
+    const size_t o_slots = cv.take(sizeof(uint16_t) * kSlotElems * size_t(n));
+    const size_t o_nel = cv.take(sizeof(int32_t) * size_t(n));
+    const size_t o_offs = cv.take(sizeof(int32_t) * size_t(n));
     b->tail_off = o_slots;
-    b->tail_bytes = off - o_slots;
+    b->tail_bytes = cv.off - o_slots;
     char* stage_mem = nullptr;
     std::vector<char> stage_vec;
     if (transient) {
-        const int rc = ws_reserve(off, std::max(in_bytes, b->tail_bytes));
+        const int rc = ws_reserve(cv.off, std::max(in_bytes, b->tail_bytes));
         if (rc) {
             free_batch(b);
             return rc;
         }
         b->owns = false;
-        b->dev = g_ws.dev;
+        b->dev = g_ws.dev.p;
         for (int k = 0; k < 3; ++k) b->ev[k] = g_ws.ev[k];
-        stage_mem = g_ws.host;
+        stage_mem = g_ws.host.p;
     } else {
-        if (hipMalloc(&b->dev, off) != hipSuccess) {
+        if (hipMalloc(&b->dev, cv.off) != hipSuccess) {
             free_batch(b);
-            return fail(HC_SW_ENOMEM, "device allocation of " + std::to_string(off) + " bytes");
+            return fail(HC_SW_ENOMEM, "device allocation of " + std::to_string(cv.off) + " bytes");
         }
         for (auto& e : b->ev) {
             if (hipEventCreate(&e) != hipSuccess) {
@@ -329,12 +296,12 @@ int run(hc_sw_batch* b, hipStream_t s)
     d.fast = b->fast;
     d.n1max = b->n1max;
     d.n2max = b->n2max;
-    HIP_TRY(hcsw_host::launch_batch(d, s, b->ev));
-    HIP_TRY(hipEventSynchronize(b->ev[2]));
+    HIP_TRY(s, hcsw_host::launch_batch(d, s, b->ev));
+    HIP_TRY(s, hipEventSynchronize(b->ev[2]));
     float a = 0, c = 0, w = 0;
-    HIP_TRY(hipEventElapsedTime(&a, b->ev[0], b->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&c, b->ev[1], b->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&w, b->ev[0], b->ev[2]));
+    HIP_TRY(s, hipEventElapsedTime(&a, b->ev[0], b->ev[1]));
+    HIP_TRY(s, hipEventElapsedTime(&c, b->ev[1], b->ev[2]));
+    HIP_TRY(s, hipEventElapsedTime(&w, b->ev[0], b->ev[2]));
     b->dp_ms += a;
     b->trace_ms += c;
     b->run_ms += w;
@@ -366,13 +333,13 @@ int results(hc_sw_batch* b, int32_t* offsets, char* cigars, int32_t stride, int3
         // [slots | n_elems | offsets] are contiguous on the device: one D2H.
         std::vector<char> tail_vec;
         char* tail = nullptr;
-        if (!b->owns && g_ws.host_bytes >= b->tail_bytes) {
-            tail = g_ws.host;
+        if (!b->owns && g_ws.host.bytes >= b->tail_bytes) {
+            tail = g_ws.host.p;
         } else {
             tail_vec.resize(b->tail_bytes);
             tail = tail_vec.data();
         }
-        HIP_TRY(hipMemcpy(tail, b->dev + b->tail_off, b->tail_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(g_stream, hipMemcpy(tail, b->dev + b->tail_off, b->tail_bytes, hipMemcpyDeviceToHost));
         const uint16_t* slotv = reinterpret_cast<const uint16_t*>(tail);
         const int32_t* cntv = reinterpret_cast<const int32_t*>(tail + (reinterpret_cast<char*>(b->n_elems) - (b->dev + b->tail_off)));
         const int32_t* offv = reinterpret_cast<const int32_t*>(tail + (reinterpret_cast<char*>(b->offsets) - (b->dev + b->tail_off)));
@@ -386,16 +353,16 @@ int results(hc_sw_batch* b, int32_t* offsets, char* cigars, int32_t stride, int3
             if (cnt[size_t(k)] <= kSlotElems) continue;
             if (P.empty()) {
                 P.resize(size_t(n));
-                HIP_TRY(hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * size_t(n), hipMemcpyDeviceToHost));
+                HIP_TRY(g_stream, hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * size_t(n), hipMemcpyDeviceToHost));
             }
             big_at[size_t(k)] = big.size();
             big.resize(big.size() + size_t(cnt[size_t(k)]));
-            HIP_TRY(hipMemcpy(big.data() + big_at[size_t(k)], b->elems + P[size_t(k)].el_off,
+            HIP_TRY(g_stream, hipMemcpy(big.data() + big_at[size_t(k)], b->elems + P[size_t(k)].el_off,
                               sizeof(uint32_t) * size_t(cnt[size_t(k)]), hipMemcpyDeviceToHost));
         }
         if (scores) {
             std::vector<SwResult> r(static_cast<size_t>(n));
-            HIP_TRY(hipMemcpy(r.data(), b->res, sizeof(SwResult) * size_t(n), hipMemcpyDeviceToHost));
+            HIP_TRY(g_stream, hipMemcpy(r.data(), b->res, sizeof(SwResult) * size_t(n), hipMemcpyDeviceToHost));
             for (int64_t k = 0; k < n; ++k) scores[b->dev_ids[size_t(k)]] = r[size_t(k)].score;
         }
         for (int64_t k = 0; k < n; ++k) {
@@ -554,9 +521,9 @@ int hc_sw_batch_stats(hc_sw_batch* b, hc_sw_stats* st)
     if (b->ran && b->nd) {
         const size_t nd = size_t(b->nd);
         std::vector<SwResult> r(nd);
-        HIP_TRY(hipMemcpy(r.data(), b->res, sizeof(SwResult) * nd, hipMemcpyDeviceToHost));
+        HIP_TRY(g_stream, hipMemcpy(r.data(), b->res, sizeof(SwResult) * nd, hipMemcpyDeviceToHost));
         std::vector<SwPair> P(nd);
-        HIP_TRY(hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * nd, hipMemcpyDeviceToHost));
+        HIP_TRY(g_stream, hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * nd, hipMemcpyDeviceToHost));
         st->cells = 0;
         for (size_t k = 0; k < nd; ++k) {
             if (r[k].shortcut) ++st->n_shortcut;
@@ -605,11 +572,12 @@ void hcphmm::sw_release()
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_stream) return;
     (void)hipStreamSynchronize(g_stream);
-    if (g_ws.dev) (void)hipFree(g_ws.dev);
-    if (g_ws.host) (void)hipHostFree(g_ws.host);
-    for (auto& e : g_ws.ev)
+    drop(g_ws.dev);
+    drop(g_ws.host);
+    for (auto& e : g_ws.ev) {
         if (e) (void)hipEventDestroy(e);
-    g_ws = Workspace{};
+        e = nullptr;
+    }
     (void)hipStreamDestroy(g_stream);
     g_stream = nullptr;
 }
