@@ -71,7 +71,7 @@ __device__ __forceinline__ void run_block(const LaneArgs& a, const LaneWave& wv,
         constexpr bool SUM = decltype(sum_tag)::value;
         if constexpr (!CG) {
             row_const<float>(a.lut, wc, wn, k);
-            mrow = mt[k.rc * 64 + lane];
+            mrow = mt[k.rc * 64 + lane];   // reloaded every row: the cells below consume it
         }
         const uint32_t wnn = row_word(cx, min(i + 2, cx.R) - 1);
         const float2 cnext = (has_in && i < wv.rmax) ? carry[size_t(i + 1) * 64] : zero;
@@ -84,7 +84,7 @@ __device__ __forceinline__ void run_block(const LaneArgs& a, const LaneWave& wv,
         }
         const int lim = (SUM && i == cx.R) ? cx.H - c0 : 0;
         float Ml = 0.f, Yl = cin.y;   // block 0: Y[i][1] = 0*my + 0*yy = 0
-        const float M0 = Tdiag * prior_of<31>(mrow.x, k.pm, k.px);
+        const float M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);
         cell<float, BC, 0, NC, SUM, EQ, true>(T, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, lim, sumM, sumX);
         if (has_out) carry[size_t(i) * 64] = make_float2(T[NC - 1], y_next<EQ>(Ml, Yl, k.my, k.yy));
         // next row's diagonal at column c0: this row's T there (block 0: column 0 -> 0)
@@ -93,7 +93,7 @@ __device__ __forceinline__ void run_block(const LaneArgs& a, const LaneWave& wv,
         if constexpr (CG) {
             k.pm = pm_n;
             k.px = px_n;
-            mrow = m_n;
+            mrow = m_n;   // a fresh window every row: the row's cells shifted the old one out
         }
         wc = wn;
         wn = wnn;
@@ -792,14 +792,14 @@ __device__ __forceinline__ bool chain_run(const Seg64Args& a, const double* __re
                 sumX = lane ? sX_in : T(0);
             }
             T Ml = T(0), Yl = y_in;
-            const T M0 = Tdiag * prior_of<31>(mrow.x, k.pm, k.px);
+            const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);
             cell<T, BC, 0, BC, SUM, true>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
             y_out = masked<AND>(y_next<true>(Ml, Yl, k.my, k.yy), keep);
             t_out = masked<AND>(Tt[BC - 1], keep);
         }
         k.pm = pm_n;
         k.px = px_n;
-        mrow = m_n;
+        mrow = m_n;   // a fresh window every step: the row's cells shifted the old one out
     };
     __builtin_amdgcn_s_waitcnt(0x0F70);
     // The chain's steps (for the issue priority): its rows and the last skew.

@@ -42,32 +42,29 @@ __device__ __forceinline__ void row_const(const T* __restrict__ lut, uint32_t wc
     k.rc = row_rc(wc);
 }
 
-// Prior of column bit `B` (MSB-first) of a match word: v_bfe_i32 (bit -> 0 /
-// -1) and one bit-select per 32-bit half (v_bitop3). The asm keeps the
-// compiler from turning it into and + cmp + cndmask.
-template <int B>
-__device__ __forceinline__ float prior_of(uint32_t w, float pm, float px)
+// Prior of the next column of a match word. The window is MSB-first and a row
+// consumes it strictly left to right, so one add with carry-out (w + w:
+// v_add_co_u32, half rate) both shifts the window one column left and puts the
+// column's bit into VCC for every lane; a VCC-form v_cndmask_b32 (e32, full
+// rate; two for a double) then picks pm or px: 3 issue slots per fp32 cell
+// where v_bfe_i32 + v_bitop3_b32 took 4, and no register besides the window
+// word, which is dead after the row anyway. Plain C, so the compiler itself
+// keeps the VCC write and its read the required wait states apart. The word is
+// consumed: the caller reloads it before its next row.
+template <typename T>
+__device__ __forceinline__ T prior_next(uint32_t& w, T pm, T px)
 {
-    int t;
-    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(t) : "v"(w), "i"(B));
-    return __int_as_float((t & __float_as_int(pm)) | (~t & __float_as_int(px)));
-}
-template <int B>
-__device__ __forceinline__ double prior_of(uint32_t w, double pm, double px)
-{
-    int t;
-    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(t) : "v"(w), "i"(B));
-    const long long a = __double_as_longlong(pm), b = __double_as_longlong(px);
-    const unsigned lo = unsigned((t & int(a)) | (~t & int(b)));
-    const unsigned hi = unsigned((t & int(a >> 32)) | (~t & int(b >> 32)));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    const bool c = __builtin_uadd_overflow(w, w, &w);
+    return c ? pm : px;
 }
 
 // Column J of one row of one block; recursion unrolls the row at compile time.
 // M enters as M[i][c0+J+1] (= T_old[J-1] * prior). Before T[J] is overwritten,
 // its old value (the next column's diagonal) is consumed into the next M, so
 // the new T[J] can take the old one's register: no copies between rows.
-// mw0/mw1: the row's match words for block columns 1-32 / 33-64.
+// mw0/mw1: the row's match words for block columns 1-32 / 33-64, consumed
+// MSB-first in column order by prior_next (the caller took column 1's bit of
+// mw0 for M; column J+1 shifts word (J+1) >> 5).
 // EQ: mx == my bitwise (insertion and deletion gap qualities equal on every
 // row: the reference's SAMRecord passes 'I' for both, sam.hpp:30-32), so the
 // product M*mx that feeds X[J] is also the M*my term of the next column's Y:
@@ -77,14 +74,36 @@ __device__ __forceinline__ double prior_of(uint32_t w, double pm, double px)
 // J < lim enter the sums (lim = columns of the block inside the hap on the
 // pair's last row, else 0).
 template <typename T, int BC, int J, int NC, bool SUM, bool EQ, bool MASK = false>
-__device__ __forceinline__ void cell(T (&Tt)[BC], T (&X)[BC], T M, T& Ml, T& Yl, uint32_t mw0, uint32_t mw1,
+__device__ __forceinline__ void cell(T (&Tt)[BC], T (&X)[BC], T M, T& Ml, T& Yl, uint32_t& mw0, uint32_t& mw1,
                                      T pm, T px, const RowConst<T>& k, int lim, T& sumM, T& sumX)
 {
     if constexpr (J < NC) {
+        // AHEAD: the shift of column J+1 is issued ahead of two independent
+        // multiplies and its select after them (scheduling barriers), so the
+        // carry's way through VCC is covered inside the wave. That pays where
+        // a wave runs alone on its SIMD (fp64 rescues, the narrow blocks of
+        // small batches); wide fp32 blocks, which run three waves per SIMD,
+        // are faster in the compiler's own order.
+        constexpr bool AHEAD = !MASK && (sizeof(T) == 8 || BC <= 32);
         T Mn = M;
-        if constexpr (J + 1 < NC)
-            Mn = Tt[J] * prior_of<31 - ((J + 1) & 31)>(((J + 1) >> 5) ? mw1 : mw0, pm, px);
+        if constexpr (!AHEAD && J + 1 < NC)
+            Mn = Tt[J] * prior_next(((J + 1) >> 5) ? mw1 : mw0, pm, px);
         const T Xc = X[J];
+        T Mm = T(0), Xg = T(0);
+        if constexpr (AHEAD) {
+            bool cb = false;
+            if constexpr (J + 1 < NC) {
+                uint32_t& w = ((J + 1) >> 5) ? mw1 : mw0;
+                cb = __builtin_uadd_overflow(w, w, &w);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            Mm = M * k.mm;
+            Xg = Xc * k.g;
+            if constexpr (J + 1 < NC) {
+                __builtin_amdgcn_sched_barrier(0);
+                Mn = Tt[J] * (cb ? pm : px);
+            }
+        }
         if constexpr (SUM && !MASK) {
             // The row sums first: they read M and the old X[J] before X[J] is
             // rewritten (after it, the old value needed a copy per column).
@@ -98,12 +117,18 @@ __device__ __forceinline__ void cell(T (&Tt)[BC], T (&X)[BC], T M, T& Ml, T& Yl,
         if constexpr (EQ) {
             const T Mx = M * k.mx;
             Y = (J == 0) ? Yl : (Ml + Yl * k.yy);
-            Tt[J] = (M * k.mm + Xc * k.g) + Y * k.g;
+            if constexpr (AHEAD)
+                Tt[J] = (Mm + Xg) + Y * k.g;
+            else
+                Tt[J] = (M * k.mm + Xc * k.g) + Y * k.g;
             X[J] = Mx + Xc * k.xx;
             Ml = Mx;
         } else {
             Y = (J == 0) ? Yl : (Ml * k.my + Yl * k.yy);
-            Tt[J] = (M * k.mm + Xc * k.g) + Y * k.g;
+            if constexpr (AHEAD)
+                Tt[J] = (Mm + Xg) + Y * k.g;
+            else
+                Tt[J] = (M * k.mm + Xc * k.g) + Y * k.g;
             X[J] = M * k.mx + Xc * k.xx;
             Ml = M;
         }
@@ -427,14 +452,14 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
         if (unsigned(i - 1) < unsigned(R)) {   // this lane's rows 1 .. R of its pair
             if constexpr (!CG) {
                 row_const<T>(lut, wc, wn, k);
-                mrow = mt[k.rc * 64 + lane];
+                mrow = mt[k.rc * 64 + lane];   // reloaded every row: the cells below consume it
             }
             if (SUM && i == R) {
                 sumM = s ? sM_in : T(0);
                 sumX = s ? sX_in : T(0);
             }
             T Ml = T(0), Yl = Yl0;
-            const T M0 = Tdiag * prior_of<31>(mrow.x, k.pm, k.px);
+            const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);   // bit 31 of mrow.x first
             cell<T, BC, 0, BC, SUM, EQ>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
             y_out = masked<AND>(y_next<EQ>(Ml, Yl, k.my, k.yy), keep);
             t_out = masked<AND>(Tt[BC - 1], keep);
@@ -445,7 +470,7 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
             // i = 0 those are row 1's, what it needs on its first row.
             k.pm = pm_n;
             k.px = px_n;
-            mrow = m_n;
+            mrow = m_n;   // a fresh window every step: the row's cells shifted the old one out
         }
         wc = wn;
     };

@@ -16,8 +16,11 @@ BC are the reading of its DPP and arithmetic counts that gives a compiled
 width (8-64, even). Issue slots price each instruction at the rates measured on
 gfx950 (tools/ubench/op_rate.hip, profiles/r02_op_rate_ubench.jsonl): 1 for
 the full-rate forms, 2 for the half-rate ones (DPP, v_bfe, v_bitop3, v_cmp,
-v_lshl_*, v_cndmask on an SGPR mask, f64 arithmetic, any VOP3 with an SGPR
-operand)."""
+v_add_co, v_lshl_*, v_cndmask on an SGPR mask, f64 arithmetic, any VOP3 with
+an SGPR operand). The prior select is v_add_co_u32 (the window shift, 2 slots)
+and the e32 v_cndmask that reads its carry from VCC (1 slot; two per fp64
+cell); s_nop (the VCC write-to-read wait states) is reported per step on its
+own: it costs issue cycles of its wave, not VALU slots."""
 import collections
 import json
 import re
@@ -27,7 +30,23 @@ FULL = {"v_mul_f32", "v_add_f32", "v_sub_f32", "v_add_u32", "v_sub_u32", "v_subr
         "v_xor_b32", "v_not_b32", "v_lshrrev_b32", "v_ashrrev_i32", "v_mov_b32", "v_mov_b64"}
 
 
-def role(op, txt):
+def writes_vcc(op, txt):
+    """Whether the instruction's destination (or carry-out) is VCC."""
+    args = [a.strip() for a in txt.split(None, 1)[1].split(",")] if " " in txt else []
+    if not args:
+        return False
+    if "_co_" in op:
+        return len(args) > 1 and args[1] == "vcc"
+    return (op.startswith("v_cmp") or op.startswith("s_")) and args[0].startswith("vcc")
+
+
+def role(op, txt, vcc_is_carry=False):
+    """vcc_is_carry: VCC was last written by a v_add_co_u32 (the window shift of
+    prior_next), so an e32 v_cndmask reading it is the prior select's."""
+    if op == "v_add_co_u32":
+        return "prior select"
+    if op == "v_cndmask_b32" and vcc_is_carry and txt.split()[0].endswith("_e32"):
+        return "prior select"
     if "_dpp" in op or " wave_shr" in txt or "row_shr" in txt:
         return "handoff (DPP)"
     if op in ("v_mul_f32", "v_add_f32", "v_mul_f64", "v_add_f64"):
@@ -115,11 +134,19 @@ def main():
         sums, steps, bc, eq = guess
         by_role = collections.Counter()
         by_slot = collections.Counter()
+        carry = False
         for op, t in ins:
-            r = role(op, t)
+            r = role(op, t, carry)
             by_role[r] += 1
             by_slot[r] += slots(op, t)
-        rows.append(dict(loop=hdr, fp64=fp64, bc=bc, eq=eq, row_sums=sums, steps_per_iteration=steps,
+            if writes_vcc(op, t):
+                carry = op == "v_add_co_u32"
+        rows.append(dict(kernel=lines[start].split(":")[0], loop=hdr, fp64=fp64, bc=bc, eq=eq, row_sums=sums, steps_per_iteration=steps,
+                         s_nop_per_step=round(c["s_nop"] / steps, 2),
+                         select_ops_per_step={k: round(c[k] / steps, 2) for k in
+                                              ("v_add_co_u32", "v_cndmask_b32", "v_bfe_i32", "v_bitop3_b32")},
+                         cndmask_e64_per_step=round(sum(1 for op, t in ins if op == "v_cndmask_b32"
+                                                        and t.split()[0].endswith("_e64")) / steps, 2),
                          arith_per_step=arith / steps,
                          instr_per_step={k: round(v / steps, 2) for k, v in by_role.items()},
                          slots_per_step={k: round(v / steps, 2) for k, v in by_slot.items()},

@@ -62,9 +62,11 @@ constexpr int ITERS = 2048;
     F(44, "v_mul_u32_u24", "v_mul_u32_u24 %0, %0, %1")                            \
     F(45, "v_and_b32_sdwa sext(BYTE_1)", "v_and_b32_sdwa %0, %1, sext(%0) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1") \
     F(46, "prior select v_bfe_i32+v_bitop3_b32(2)", "v_bfe_i32 %0, %1, %0, 1\n v_bitop3_b32 %0, %0, %1, %1 bitop3:0xe4") \
-    F(47, "prior select v_and_b32_sdwa+v_xor_b32(2)", "v_and_b32_sdwa %0, %1, sext(%0) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n v_xor_b32 %0, %0, %1")
+    F(47, "prior select v_and_b32_sdwa+v_xor_b32(2)", "v_and_b32_sdwa %0, %1, sext(%0) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n v_xor_b32 %0, %0, %1") \
+    F(48, "v_add_co_u32+v_cndmask_b32(2)", "v_add_co_u32 %0, vcc, %0, %0\n v_cndmask_b32 %0, %0, %1, vcc") \
+    F(49, "v_add_co_u32+s_nop 1+v_cndmask_b32(2)", "v_add_co_u32 %0, vcc, %0, %0\n s_nop 1\n v_cndmask_b32 %0, %0, %1, vcc")
 
-constexpr int NOPS = 48;
+constexpr int NOPS = 50;
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k(int* out, int c)
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(256) void k(int* out, int c)
 #define CASE(ID, NAME, ASM)                                                 \
     if constexpr (MODE == ID) {                                             \
         _Pragma("unroll") for (int i = 0; i < 16; ++i)                      \
-            { if constexpr (ID == 27 || ID == 28 || ID == 29 || ID == 34 || ID == 18) asm volatile(ASM : "+v"(a[i]) : "v"(c) : "vcc"); \
+            { if constexpr (ID == 27 || ID == 28 || ID == 29 || ID == 34 || ID == 18 || ID == 48 || ID == 49) asm volatile(ASM : "+v"(a[i]) : "v"(c) : "vcc"); \
               else asm volatile(ASM : "+v"(a[i]) : "v"(c)); }                \
     }
         OPS(CASE)
@@ -139,7 +141,7 @@ void all(int* out, int blocks)
             OPS(NAME)
 #undef NAME
         };
-        g_per = (M == 34 || M == 46 || M == 47) ? 2 : (M == 40) ? 3 : 1;
+        g_per = (M == 34 || M == 46 || M == 47 || M == 48 || M == 49) ? 2 : (M == 40) ? 3 : 1;
         report(names[M], run(k<M>, out, blocks));
         g_per = 1;
         all<M + 1>(out, blocks);
