@@ -298,7 +298,7 @@ int grid_policy(const Local& loc, const int32_t* rlen, CandOf&& hcand, const flo
 // block's mean read length), the block's haps are grouped by (BC, nb) and its
 // reads sorted by R, and a group's pairs in (read by R descending) x (hap)
 // order fill waves of floor(64 / nb) pairs — the order the general planner's
-// sort + greedy packing reaches on such a batch, built in one parallel pass
+// sort + packing reaches on such a batch, built in one parallel pass
 // over segments (one per block and group; a segment's last wave may be
 // partial). Segments run widest block first, so co-resident waves share a
 // width's code. Writes every pair's descriptor, the slot order and the waves;
@@ -789,22 +789,29 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
             }
         });
         tm.mark("pairs");
+        // Sorted by (BC, steps = R + nb - 1) descending: a wave runs the most
+        // steps of its pairs, and one width holds nb from 2 to about 10, so by
+        // (BC, R) the groups of few lanes finished early and idled (0.011 of
+        // S2's swept lane-cells). nb <= 64 widens the key range.
         if (!seg_in.empty()) {
-            const int rlo = rmin_a.load(), rspan = rmax_a.load() - rlo + 1;
-            const int nbk = (kSegMaxBC / 2 + 1) * rspan;
+            const int rlo = rmin_a.load(), sspan = rmax_a.load() - rlo + 64;
+            const int nbk = (kSegMaxBC / 2 + 1) * sspan;
             if (nbk <= (1 << 18)) {
-                counting_sort_desc(seg_in, S.sort_tmp, S.hist, nbk,
-                                   [&](int p) { return (seg_bc[size_t(p)] / 2) * rspan + (pd[p].y - rlo); });
+                counting_sort_desc(seg_in, S.sort_tmp, S.hist, nbk, [&](int p) {
+                    return (seg_bc[size_t(p)] / 2) * sspan + (pd[p].y - rlo + seg_nb[size_t(p)] - 1);
+                });
             } else {
                 std::vector<uint32_t>& key = S.key;
                 grow(key, size_t(npairs));
-                for (int p : seg_in) key[size_t(p)] = (uint32_t(seg_bc[size_t(p)]) << 16) | uint32_t(std::min(pd[p].y, 65535));
+                for (int p : seg_in)
+                    key[size_t(p)] = (uint32_t(seg_bc[size_t(p)]) << 16) |
+                                     uint32_t(std::min(pd[p].y + seg_nb[size_t(p)] - 1, 65535));
                 sort_desc(seg_in, key);
             }
         }
         tm.mark("seg sort");
-        // Greedy packing in independent segments of the sorted list (one per task;
-        // a segment boundary costs at most one partly filled wave).
+        // Packing in independent segments of the sorted list (one per task; a
+        // segment boundary costs at most one partly filled wave).
         const int64_t ns = int64_t(seg_in.size());
         seg_ord.resize(size_t(ns));
         {
@@ -847,6 +854,16 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
                 auto& W = part_w[size_t(t)];
                 int64_t slot_n = b;
                 constexpr int64_t kLook = 64;
+                // Knapsack over the free lanes: best[kLook + c] is the largest
+                // sum of nb * steps of the items seen so far on at most c lanes
+                // (entries below kLook stand for c < 0), take[k][c] whether
+                // item k raised it. Fixed trip counts, so the loops vectorise.
+                constexpr int32_t kNever = -(1 << 30);
+                int32_t bufa[2 * kLook], bufb[2 * kLook];
+                std::fill(bufa, bufa + kLook, kNever);
+                std::fill(bufb, bufb + kLook, kNever);
+                uint8_t take[kLook][kLook];
+                int item_j[kLook], item_nb[kLook];
                 for (int64_t i = 0; i < m; ++i) {
                     if (used[i]) continue;
                     const int bc = int(rec[i] & 0xff);
@@ -854,23 +871,75 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
                     w.slot0 = int(slot_n);
                     w.ncols = bc;
                     int rmin = INT32_MAX, rmax = 0, nst = 0, np = 0;
-                    int free = 64;
-                    const int need = minnb[size_t(bc)];
-                    const int64_t jend = std::min(m, i + kLook);
-                    for (int64_t j = i; j < jend && free >= need; ++j) {
-                        if (used[j]) continue;
+                    auto put = [&](int64_t j) {
                         const uint32_t r = rec[j];
-                        if (int(r & 0xff) != bc) break;
-                        const int nb = int((r >> 8) & 0xff);
-                        if (nb > free) continue;
+                        const int nb = int((r >> 8) & 0xff), R = int(r >> 16);
                         used[j] = 1;
-                        free -= nb;
                         ordo[slot_n++] = in[j];
                         ++np;
-                        const int R = int(r >> 16);
                         rmax = R > rmax ? R : rmax;
                         rmin = R < rmin ? R : rmin;
                         nst = R + nb - 1 > nst ? R + nb - 1 : nst;
+                    };
+                    // The first unused pair opens the wave: no later entry of
+                    // the sorted list runs more steps, so none lengthens it.
+                    put(i);
+                    const int cap = 64 - int((rec[i] >> 8) & 0xff);
+                    if (cap >= minnb[size_t(bc)]) {
+                        // Of the unused pairs of this width in the window, the
+                        // subset on at most cap lanes with the largest sum of
+                        // nb * steps: in effect full lanes first, then the longest pairs.
+                        // Only the first cap / nb pairs of one nb can matter.
+                        uint8_t seen[kLook + 1] = {};
+                        int32_t* cur = bufa + kLook;
+                        int32_t* nxt = bufb + kLook;
+                        std::fill(cur, cur + kLook, 0);
+                        int n = 0;
+                        const int64_t jend = std::min(m, i + kLook);
+                        for (int64_t j = i + 1; j < jend; ++j) {
+                            if (used[j]) continue;
+                            const uint32_t r = rec[j];
+                            if (int(r & 0xff) != bc) break;
+                            const int nb = int((r >> 8) & 0xff);
+                            if (nb > cap || (seen[nb] + 1) * nb > cap) continue;
+                            ++seen[nb];
+                            const int32_t v = int32_t(nb) * (int32_t(r >> 16) + nb - 1);
+                            const int32_t* __restrict from = cur - nb;
+                            const int32_t* __restrict keep = cur;
+                            int32_t* __restrict to = nxt;
+                            uint8_t* __restrict tk = take[n];
+                            for (int c = 0; c < int(kLook); ++c) {
+                                const int32_t with = from[c] + v;
+                                const bool t = with > keep[c];   // ties stay with the earlier pairs
+                                tk[c] = t;
+                                to[c] = t ? with : keep[c];
+                            }
+                            std::swap(cur, nxt);
+                            item_j[n] = int(j - i);
+                            item_nb[n] = nb;
+                            ++n;
+                            // No later pair runs more steps than this one, so
+                            // they add at most `steps` per lane still free:
+                            // once no fill can pass best[cap] that way, the
+                            // rest of the window changes nothing.
+                            if (n % 4 == 0) {
+                                const int32_t steps = int32_t(r >> 16) + nb - 1;
+                                const int32_t* __restrict at = cur;
+                                int32_t bound = 0;
+                                for (int c = 0; c <= cap; ++c) {
+                                    const int32_t x = at[c] + (cap - c) * steps;
+                                    bound = x > bound ? x : bound;
+                                }
+                                if (bound <= cur[cap]) break;
+                            }
+                        }
+                        int c = cap, nsel = 0, sel[kLook];
+                        for (int k = n - 1; k >= 0; --k)
+                            if (take[k][c]) {
+                                sel[nsel++] = item_j[k];
+                                c -= item_nb[k];
+                            }
+                        for (int k = nsel - 1; k >= 0; --k) put(i + sel[k]);
                     }
                     w.npairs = np;
                     w.rmax = rmax;
@@ -885,7 +954,7 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
             for (auto& W : part_w) lw.insert(lw.end(), W.begin(), W.end());
         }
     }
-    tm.mark("seg pack: greedy");
+    tm.mark("seg pack: fill");
     // Dispatch order: the bulk in packing order (co-resident waves share one
     // width's code), the shortest waves filling the last tail_rounds rounds of
     // wave slots last, longest first (LPT, duration ~ BC * nsteps), so the chip
