@@ -86,7 +86,7 @@ struct Slot {
     // k + 1 and the kernels of part k, and its kernels fill the chip together).
     hipStream_t stream = nullptr, side = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;   // side-stream fork / join (timing disabled)
-    hipEvent_t ev[7] = {};   // pack [2], fp32 / fp64 pass [3], done, early results: reused by every part in the slot
+    hipEvent_t ev[7] = {};   // pack [2], fp32 / fp64 pass [3], done, early results: reused by every part in the slot (bind_streams)
     hipEvent_t up_ev[2] = {};   // staging halves: H2D of a half done (timing disabled)
 };
 
@@ -366,10 +366,15 @@ private:
     Part* p_;
 };
 
-// planner.cpp: plan one part on device d (host planning + staging, then the
-// H2D, device packing and, with_run, the device pass and the D2H of the
-// results, all enqueued on the part's stream). slot == nullptr: the part owns
-// its memory (batches). Dry runs stop after planning (*out = nullptr).
+// planner.cpp: plan one part on device d. A driver over named stages:
+// scan_inputs, upload_layout + staging_memory, classify_haps, then
+// choose_grid_policy + plan_grid (cross products) or plan_general
+// (classify_pairs, sort_seg_pairs, pack_seg_waves), reorder_tail,
+// bin_lane_and_diag, fill_staging; dry runs stop there (keep_dry_dump,
+// *out = nullptr); then device_layout, bind_part and enqueue_upload (the H2D,
+// device packing and, with_run, the device pass and the D2H of the results,
+// all on the part's stream). slot == nullptr: the part owns its memory
+// (batches). part_setup.hpp holds what it shares with plan_flat_device.
 int plan_part(Device& d, const Src& src, const PartSpec& spec, Slot* slot, bool with_run, PlanMode mode,
               Part** out);
 // flat_plan.cpp: a flat part whose pairs are planned on the device; returns
@@ -391,6 +396,9 @@ void finish_part(const Part& P, const float* f, const double* d, const uint8_t* 
 // base k in the low nibble of byte k / 2 when k is even (AVX2 when the CPU
 // has it; flat_plan.cpp).
 void pack_nibbles(const uint8_t* s, int n, uint8_t* d);
+// Whether a read's (i, d, c) gap qualities are the same on every row (then
+// they travel once, in its descriptor; flat_plan.cpp).
+bool constant_gaps(const uint8_t* i, const uint8_t* d, const uint8_t* c, int len);
 int enqueue_results(Part* b, hipStream_t s);
 int check_device_error(const int* counters);   // run.cpp: counters = a host copy of a part's run counters
 

@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "engine_core.hpp"
+#include "part_setup.hpp"
 #include "plan_model.hpp"
 #include "pool.hpp"
 
@@ -54,12 +55,6 @@ struct FlatScratch {
     std::vector<int32_t> hsamp;
 };
 thread_local FlatScratch t_fs;
-
-template <typename T>
-void grow(std::vector<T>& v, size_t n)
-{
-    if (v.size() < n) v.resize(n);
-}
 
 // Gap qualities of a read constant over its rows (blocks of 64 without early
 // exit inside a block, so the compiler vectorises the compare).
@@ -108,11 +103,6 @@ bool has_avx2()
 {
     static const bool v = __builtin_cpu_supports("avx2");
     return v;
-}
-
-bool constant_gaps(const uint8_t* i, const uint8_t* d, const uint8_t* c, int len)
-{
-    return has_avx2() ? constant_gaps_avx2(i, d, c, len) : constant_gaps_scalar(i, d, c, len);
 }
 
 constexpr int align4(int x) { return (x + 3) & ~3; }
@@ -207,6 +197,11 @@ __attribute__((target("avx2"))) void copy_bytes_avx2(const uint8_t* __restrict s
 }
 
 }  // namespace
+
+bool constant_gaps(const uint8_t* i, const uint8_t* d, const uint8_t* c, int len)
+{
+    return has_avx2() ? constant_gaps_avx2(i, d, c, len) : constant_gaps_scalar(i, d, c, len);
+}
 
 void copy_bytes(const uint8_t* s, int n, uint8_t* d)
 {
@@ -505,6 +500,12 @@ bool default_policies()
 
 namespace {
 
+// plan_flat_try's HC_PHMM_* settings, read once at its top.
+struct FlatSettings {
+    int64_t tail_rounds = std::max<int64_t>(0, env_i64("HC_PHMM_TAIL_ROUNDS", 2));
+    int prep_blocks = int(env_i64("HC_PHMM_PREP_BLOCKS", 0));
+};
+
 // One attempt: scan_gaps = false assumes constant gap qualities and format
 // fmt0 everywhere (checked in pass 2; kRetryWithPlanes / kRetryNibbles if
 // not), true finds each pair's in pass 1. record_rate: this attempt's host
@@ -515,6 +516,7 @@ int plan_flat_try(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, 
 {
     *out = nullptr;
     PhaseTimer tm;
+    const FlatSettings cfg;
     using clk = std::chrono::steady_clock;
     const clk::time_point t_begin = clk::now();
     clk::duration t_stage{};   // scan + fill: the host staging rate (Device::stage_ps_per_cell)
@@ -627,26 +629,13 @@ int plan_flat_try(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, 
     // Device layout: the upload image, descriptors and tables, then what the
     // device builds, the outputs and the rescue scratch.
     const size_t n1 = size_t(n);
-    const ResLayout RL = res_layout(n1);
-    const size_t res_bytes = RL.bytes;
-    struct Lay {
-        size_t off = 0;
-        size_t take(size_t b)
-        {
-            const size_t o = off;
-            off += (b + 255) & ~size_t(255);
-            return o;
-        }
-    } L;
+    Layout L;
     const size_t o_img = L.take(size_t(rec) + 16);
     const size_t o_desc = L.take(sizeof(FlatDesc) * n1);
     const size_t tab_bytes = sizeof(int2) * (size_t(hmax) + 1) + sizeof(float) * 65 + sizeof(int2) * size_t(ngroups);
     const size_t o_tab = L.take(tab_bytes);
-    const size_t row_pad = kRowPadBefore + size_t(rmax) + 256;
-    if (int64_t(rows) + int64_t(row_pad) > kMaxRowWords)
-        return fail(HC_PHMM_EINVAL, "batch too large (read bases of one part exceed 2^30)");
-    if (int64_t(hapw) + 16 > kMaxHapWords)
-        return fail(HC_PHMM_EINVAL, "batch too large (hap match tables of one part exceed 2^30 words)");
+    const size_t row_pad = row_pad_words(rmax);
+    if (const int bad = check_pool_words(rows, row_pad, hapw)) return bad;
     const size_t o_rows = L.take(sizeof(uint32_t) * (size_t(rows) + row_pad));
     const size_t o_hapw = L.take(sizeof(uint32_t) * (size_t(hapw) + 16));
     const size_t o_pairs = L.take(sizeof(PairDesc) * n1);
@@ -656,21 +645,14 @@ int plan_flat_try(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, 
     const size_t o_order = L.take(sizeof(int) * n1);
     const size_t o_waves = L.take(sizeof(LaneWave) * size_t(max_waves));
     // The last two rounds of wave slots (3 per SIMD) dispatched longest first
-    // (planner.cpp: 125k-pair shard 1.39 -> 1.25 ms with it on the host plan).
-    const int tail = int(std::max<int64_t>(0, env_i64("HC_PHMM_TAIL_ROUNDS", 2))) * 4 * dv.n_cu * 3;
+    // (planner.cpp reorder_tail: 125k-pair shard 1.39 -> 1.25 ms with it on the host plan).
+    const int tail = int(cfg.tail_rounds) * 4 * dv.n_cu * 3;
     const size_t o_wtmp = L.take(tail > 0 ? sizeof(LaneWave) * size_t(max_waves) : 0);
     const size_t o_wcost = L.take(tail > 0 ? sizeof(int) * size_t(max_waves) : 0);
     const size_t o_nw = L.take(2 * sizeof(int));   // wave count, then the largest modelled wave cost
-    const size_t o_res = L.take(res_bytes);
-    const size_t o_list = L.take(2 * sizeof(int) * n1);   // pair ids, then pack_rh (Seg64Args::list_rh)
-    const size_t o_rec = L.take(sizeof(uint4) * n1);   // seg slot records (every pair is a seg pair)
+    const RescueLayout RS = take_rescue(L, n1, n1);   // every pair is a seg pair: n1 slots
+    const size_t res_bytes = RS.RL.bytes;
     const size_t o_slotof = L.take(sizeof(int) * n1);
-    const size_t o_sdesc = L.take(sizeof(PairDesc) * n1);
-    const size_t o_sorted = L.take(sizeof(int) * n1);
-    const size_t o_worder = L.take(sizeof(int) * n1);
-    const size_t o_big = L.take(sizeof(int) * n1);
-    const size_t o_bigc = L.take(sizeof(int));
-    const size_t o_plan = L.take(sizeof(Seg64Plan));
     const size_t total = L.off;
     const size_t host_res_off = (tab_bytes + 255) & ~size_t(255);
     // Jobs borrow their slot's workspace; batches (slot == nullptr) own their
@@ -733,42 +715,11 @@ int plan_flat_try(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, 
     b->d_hapw = reinterpret_cast<uint32_t*>(dev + o_hapw);
     b->d_lane_order = reinterpret_cast<int*>(dev + o_order);
     b->d_lane_waves = reinterpret_cast<LaneWave*>(dev + o_waves);
-    b->res_bytes = res_bytes;
-    b->res_o64 = RL.o64;
-    b->res_ofl = RL.ofl;
-    b->res_ocnt = RL.ocnt;
-    b->own_raw32 = b->d_raw32 = reinterpret_cast<float*>(dev + o_res);
-    b->own_raw64 = b->d_raw64 = reinterpret_cast<double*>(dev + o_res + RL.o64);
-    b->own_flag = b->d_flag = reinterpret_cast<uint8_t*>(dev + o_res + RL.ofl);
-    b->d_list = reinterpret_cast<int*>(dev + o_list);
-    b->d_count = reinterpret_cast<int*>(dev + o_res + RL.ocnt);   // run counters: the results block's tail
-    b->d_sorted = reinterpret_cast<int*>(dev + o_sorted);
-    b->d_worder = reinterpret_cast<int*>(dev + o_worder);
-    b->d_big = reinterpret_cast<int*>(dev + o_big);
-    b->d_big_count = reinterpret_cast<int*>(dev + o_bigc);
-    b->d_plan = reinterpret_cast<Seg64Plan*>(dev + o_plan);
-    b->d_rec = reinterpret_cast<uint4*>(dev + o_rec);
+    bind_rescue(*b, dev, RS, n1);
     b->d_slot_of = reinterpret_cast<int*>(dev + o_slotof);
-    b->d_sdesc = reinterpret_cast<PairDesc*>(dev + o_sdesc);
     b->n_wide = nwide;
-    if (slot) {
-        b->host_res = host + host_res_off;
-        b->stream = slot->stream;
-        b->side = slot->side;
-        b->fork = slot->fork;
-        b->join = slot->join;
-        b->slot_ev = true;
-        b->pack_ev[0] = slot->ev[0];
-        b->pack_ev[1] = slot->ev[1];
-        b->ev_pool.push_back({slot->ev[2], slot->ev[3], slot->ev[4]});
-        b->done = slot->ev[5];
-        b->early = slot->ev[6];
-    } else {
-        b->stream = dv.stream;
-        b->side = dv.side;
-        b->fork = dv.fork;
-        b->join = dv.join;
-    }
+    if (slot) b->host_res = host + host_res_off;
+    bind_streams(*b, dv, slot);
     b->upload_bytes = size_t(rec) + sizeof(FlatDesc) * n1 + tab_bytes;
     hipStream_t s = b->stream;
 
@@ -848,7 +799,7 @@ int plan_flat_try(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, 
         a.max_waves = int(max_waves);
         a.nwaves = reinterpret_cast<int*>(dev + o_nw);
         a.counters = b->d_count;
-        a.prep_blocks = int(env_i64("HC_PHMM_PREP_BLOCKS", 0));
+        a.prep_blocks = cfg.prep_blocks;
         HIP_TRY(launch_flat_plan(a, ps));
         HIP_TRY(hipEventRecord(b->pack_ev[1], ps));
         if (with_run) {

@@ -12,8 +12,10 @@
 
 #include "engine_core.hpp"
 #include "luts.hpp"
+#include "part_setup.hpp"
 #include "plan_model.hpp"
 #include "pool.hpp"
+#include "seg_pack.hpp"
 
 namespace hcphmm {
 namespace eng {
@@ -22,8 +24,6 @@ namespace {
 constexpr int kW64Threshold = 768;     // anti-diagonal kernel: H above this -> one pair per wave
 constexpr int kLaneMaxH = 4096;        // longer haps stay on the anti-diagonal kernel (policy "auto")
 constexpr int kSegWavesPerSimd = 3;    // resident seg waves per SIMD (phmm_seg_kernel occupancy)
-
-int lane_variant_id() { return int(env_i64("HC_PHMM_LANE_VARIANT", 0)); }
 
 // HC_PHMM_LANE_SEG = auto (default) | all | off. Returns -1 auto, 0 off, 1 all.
 int lane_seg_policy()
@@ -41,6 +41,27 @@ int kernel_policy()
     if (!std::strcmp(e, "lane")) return 1;
     return 2;
 }
+
+// The planner's HC_PHMM_* settings, read once at the top of plan_part.
+struct Settings {
+    int kernel = kernel_policy();
+    int lane_seg = lane_seg_policy();
+    int lane_variant = int(env_i64("HC_PHMM_LANE_VARIANT", 0));
+    int64_t seg_cap = env_i64("HC_PHMM_SEG_CAP", 0);        // > 0: forces the width cap
+    int seg_q = int(env_i64("HC_PHMM_SEG_Q", -1));          // sweeps: force the nb0 (0) or nb0 + 1 (1) candidate
+    bool grid_plan = env_i64("HC_PHMM_GRID_PLAN", 1) != 0;   // 0 forces the general planner (A/B, tests)
+    bool grid_policy = env_i64("HC_PHMM_GRID_POLICY", 1) != 0;
+    bool grid_caps = env_i64("HC_PHMM_GRID_CAPS", 1) != 0;
+    // Pairs per planning task (a 415 x 128 region call on the GPU box: 2.0 ms
+    // at 8192, 2.96 ms on one task; tools/region_ab.py).
+    int64_t task_pairs = std::max<int64_t>(1024, env_i64("HC_PHMM_TASK_PAIRS", 8192));
+    int64_t tail_rounds = env_i64("HC_PHMM_TAIL_ROUNDS", INT64_MIN);   // INT64_MIN: unset (reorder_tail's default)
+    // Reads (haps) per staging task: a region's few hundred reads go on this
+    // thread alone below HC_PHMM_FILL_GRAIN (a pool wake-up cost about what
+    // the packing of 415 reads does).
+    int64_t fill_grain = std::max<int64_t>(1, env_i64("HC_PHMM_FILL_GRAIN", 256));
+    int64_t zero_copy_max = env_i64("HC_PHMM_ZERO_COPY_MAX", int64_t(4) << 20);
+};
 
 // LSD radix sort of `idx` by a 32-bit key, DESCENDING, stable (fallback of
 // the counting sort when the key range is wide).
@@ -90,34 +111,6 @@ void counting_sort_desc(std::vector<int>& idx, std::vector<int>& out, std::vecto
         for (int64_t k = t * chunk, e = std::min(n, k + chunk); k < e; ++k) out[h[bucket(idx[k])]++] = idx[k];
     });
     idx.swap(out);
-}
-
-// Bump allocator over one region: 256-B aligned segments.
-struct Layout {
-    size_t off = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = off;
-        off += (bytes + 255) & ~size_t(255);
-        return o;
-    }
-};
-
-// Whether a read's (i, d, c) gap qualities are the same on every row (then
-// they travel once, in its descriptor). Blocks of 64 rows without early exit
-// inside a block, so the compiler vectorises the compare.
-bool constant_gaps(const ReadView& v)
-{
-    const uint8_t i0 = v.i[0], d0 = v.d[0], c0 = v.c[0];
-    int k = 0;
-    for (; k + 64 <= v.len; k += 64) {
-        uint8_t a = 0;
-        for (int j = 0; j < 64; ++j) a |= uint8_t((v.i[k + j] ^ i0) | (v.d[k + j] ^ d0) | (v.c[k + j] ^ c0));
-        if (a) return false;
-    }
-    uint8_t a = 0;
-    for (; k < v.len; ++k) a |= uint8_t((v.i[k] ^ i0) | (v.d[k] ^ d0) | (v.c[k] ^ c0));
-    return a == 0;
 }
 
 // The part's reads / haps in part-local order, and the (read, hap) of each
@@ -214,13 +207,6 @@ struct PlanScratch {
     std::vector<int64_t> hist;
 };
 thread_local PlanScratch t_scr;
-
-template <typename T>
-void grow(std::vector<T>& v, size_t n)
-{
-    if (v.size() < n) v.resize(n);
-}
-
 
 // The candidate policy of a structured plan: each hap's cheaper candidate
 // (-1), or candidate 0 / 1 for every hap, whichever the pass model prices
@@ -437,22 +423,24 @@ int64_t plan_grid(const Local& loc, const int32_t* rlen, const int32_t* hlen, co
     return cells.load();
 }
 
-// Plan one part on device d: host binning + staging, then the H2D, device
-// packing and (with_run) the device pass and the D2H of the results, all
-// enqueued on d's stream. slot == nullptr: the part owns its memory (batches).
-}  // namespace
+// ---- The stages of plan_part, in the order they run. Each takes what it
+// reads and returns what it makes; the large arrays live in the PlanScratch.
 
-int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool with_run, PlanMode mode,
-              Part** out)
+constexpr int kDiagW[2] = {16, 64};   // anti-diagonal classes: W by H
+
+// Lengths and pool offsets of the part's reads and haps (arrays of the scratch).
+struct Scan {
+    const int32_t *rlen, *gapw, *hlen;   // gapw: a read's constant gap triple, -1 if its gap qualities vary
+    const int64_t *row_off, *gap_off, *hap_w, *hap_b;   // prefix sums (one past the last: the totals)
+    int64_t nrows, ngap, rows_sum;
+    int rlen_max;
+};
+
+// Reads: validate, lengths, gap-quality constancy; haps: validate, lengths.
+int scan_inputs(const Local& loc, PlanScratch& S, Scan& sc)
 {
-    const bool dry = mode == PlanMode::Dry;
-    PhaseTimer tm;
-    Local loc(src, spec);
-    const int64_t nr = loc.nr, nh = loc.nh, npairs = loc.np;
-    if (npairs > (int64_t(1) << 31) - 1) return fail(HC_PHMM_EINVAL, "too many pairs for one batch");
-
-    // Reads: validate, lengths, gap-quality constancy; haps: validate, lengths.
-    PlanScratch& S = t_scr;
+    const Src& src = *loc.src;
+    const int64_t nr = loc.nr, nh = loc.nh;
     grow(S.rlen, size_t(nr));
     grow(S.gapw, size_t(nr));
     grow(S.hlen, size_t(nh));
@@ -475,8 +463,10 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
             rlen[size_t(r)] = v.len;
             rm = std::max(rm, v.len);
             rs += v.len;
-            gapw[size_t(r)] = constant_gaps(v) ? int32_t((v.i[0] & 127) | ((v.d[0] & 127) << 7) | ((v.c[0] & 127) << 14))
-                                               : -1;
+            // constant (i, d, c) gap qualities travel once, in the read's descriptor
+            gapw[size_t(r)] = constant_gaps(v.i, v.d, v.c, v.len)
+                                  ? int32_t((v.i[0] & 127) | ((v.d[0] & 127) << 7) | ((v.c[0] & 127) << 14))
+                                  : -1;
         }
         rows_sum.fetch_add(rs);
         int cur = rlen_max.load();
@@ -507,69 +497,102 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
     const int64_t nrows = row_off[size_t(nr)], ngap = gap_off[size_t(nr)];
     if (nrows > INT32_MAX || hap_w[size_t(nh)] > INT32_MAX || hap_b[size_t(nh)] > INT32_MAX || ngap > INT32_MAX)
         return fail(HC_PHMM_EINVAL, "batch too large (row or hap pool exceeds 2^31)");
-    tm.mark("reads/haps scan");
+    sc = Scan{rlen, gapw, hlen, row_off.data(), gap_off.data(), hap_w.data(), hap_b.data(),
+              nrows, ngap, rows_sum.load(), rlen_max.load()};
+    return HC_PHMM_OK;
+}
 
-    // Staging layout (upload part first; waves last, their count is known later).
+// Offsets of the staging image (upload part first; waves last, their count is
+// known later), and the sizes of the buffer that holds it.
+struct UploadLayout {
+    size_t o_pairs, o_rd, o_hd, o_ord, o_slotof, o_bases, o_quals, gap_stride, o_gaps, o_hb, o_lw;
+    size_t upload_cap, res_off, res_bytes;   // the image's bound, then (slots) the results image
+};
+
+UploadLayout upload_layout(const Local& loc, const Scan& sc)
+{
+    const int64_t nr = loc.nr, nh = loc.nh, npairs = loc.np;
+    UploadLayout u;
     Layout U;
-    const size_t o_pairs = U.take(sizeof(PairDesc) * size_t(npairs));
-    const size_t o_rd = U.take(sizeof(int4) * size_t(nr));
-    const size_t o_hd = U.take(sizeof(int4) * size_t(nh));
-    const size_t o_ord = U.take(sizeof(int) * size_t(npairs));
-    const size_t o_slotof = U.take(sizeof(int) * size_t(npairs));   // pair -> seg slot (-1: other kernels)
-    const size_t o_bases = U.take(size_t(nrows) / 2 + 16);
-    const size_t o_quals = U.take(size_t(nrows) + 16);
-    const size_t gap_stride = (size_t(ngap) + 16 + 15) & ~size_t(15);
-    const size_t o_gaps = U.take(ngap ? 3 * gap_stride : 0);
-    const size_t o_hb = U.take(size_t(hap_b[size_t(nh)]) + 16);
-    const size_t o_lw = U.off;   // LaneWave array, sized after packing
-
-    // Pinned staging: upper bound for the waves (one per seg pair at most, plus
-    // one-lane waves) and the results image after the upload.
-    const size_t waves_max = sizeof(LaneWave) * (size_t(npairs) + 1) + sizeof(GridBlock) * spec.blocks.size() +
+    u.o_pairs = U.take(sizeof(PairDesc) * size_t(npairs));
+    u.o_rd = U.take(sizeof(int4) * size_t(nr));
+    u.o_hd = U.take(sizeof(int4) * size_t(nh));
+    u.o_ord = U.take(sizeof(int) * size_t(npairs));
+    u.o_slotof = U.take(sizeof(int) * size_t(npairs));   // pair -> seg slot (-1: other kernels)
+    u.o_bases = U.take(size_t(sc.nrows) / 2 + 16);
+    u.o_quals = U.take(size_t(sc.nrows) + 16);
+    u.gap_stride = (size_t(sc.ngap) + 16 + 15) & ~size_t(15);
+    u.o_gaps = U.take(sc.ngap ? 3 * u.gap_stride : 0);
+    u.o_hb = U.take(size_t(sc.hap_b[size_t(nh)]) + 16);
+    u.o_lw = U.off;   // LaneWave array, sized after packing
+    // Upper bound for the waves (one per seg pair at most, plus one-lane
+    // waves) and the results image after the upload.
+    const size_t waves_max = sizeof(LaneWave) * (size_t(npairs) + 1) + sizeof(GridBlock) * loc.spec->blocks.size() +
                              sizeof(GridSeg) * size_t(nh) + sizeof(int) * size_t(nr + nh) + 1024;
-    const size_t n1 = size_t(std::max<int64_t>(npairs, 1));
-    const ResLayout RL = res_layout(n1);
-    const size_t res_bytes = RL.bytes;
-    const size_t host_upload_cap = o_lw + waves_max;
-    const size_t host_res_off = (host_upload_cap + 255) & ~size_t(255);
+    u.upload_cap = u.o_lw + waves_max;
+    u.res_off = (u.upload_cap + 255) & ~size_t(255);
+    u.res_bytes = res_layout(size_t(std::max<int64_t>(npairs, 1))).bytes;
+    return u;
+}
+
+// The staging buffer: plain memory (dry runs), the slot's pinned area, or a
+// pinned buffer the part owns, freed when its planning returns.
+struct Staging {
     char* host = nullptr;
-    bool own_host = false;
+    bool own = false;
+    Staging() = default;
+    Staging(const Staging&) = delete;
+    ~Staging()
+    {
+        if (own && host) (void)hipHostFree(host);
+    }
+};
+
+int staging_memory(const UploadLayout& U, Slot* slot, bool dry, Staging& st)
+{
     thread_local std::vector<char> dry_host;   // dry runs: plain memory
     if (dry) {
-        if (dry_host.size() < host_res_off + res_bytes) dry_host.resize(host_res_off + res_bytes);
-        host = dry_host.data();
+        grow(dry_host, U.res_off + U.res_bytes);
+        st.host = dry_host.data();
     } else if (slot) {
-        const int rc = slot_reserve(*slot, 0, host_res_off + res_bytes);
+        const int rc = slot_reserve(*slot, 0, U.res_off + U.res_bytes);
         if (rc) return rc;
-        host = slot->host;
+        st.host = slot->host;
     } else {
-        if (hipHostMalloc(&host, std::max<size_t>(host_upload_cap, 1), hipHostMallocPortable) != hipSuccess)
+        if (hipHostMalloc(&st.host, std::max<size_t>(U.upload_cap, 1), hipHostMallocPortable) != hipSuccess) {
+            st.host = nullptr;
             return fail(HC_PHMM_ENOMEM, "pinned staging buffer");
-        own_host = true;
-    }
-    struct HostGuard {
-        char* p;
-        bool own;
-        ~HostGuard()
-        {
-            if (own && p) (void)hipHostFree(p);
         }
-    } hguard{host, own_host};
-    tm.mark("staging alloc");
+        st.own = true;
+    }
+    return HC_PHMM_OK;
+}
 
-    // Per hap: kernel class, lanes at each width cap (times the reads it pairs
-    // with), then the pass's cap and the hap's two (BC, nb) candidates.
-    PairDesc* pd = reinterpret_cast<PairDesc*>(host + o_pairs);
-    const int pol = kernel_policy();
+struct HapClasses {
+    const uint8_t* hcls;   // class: 0 seg, 1 one-lane, 2 diag W16, 3 diag W64
+    Cand* hcand;           // the two (BC, nb) candidates of each class-0 hap
+    int hmax;
+    int64_t n_wide;        // pairs whose hap is beyond the fp64 segmented kernel's reach
+    int cap;
+    const float* waste;
+};
+
+// Per hap: kernel class, lanes at each width cap (times the reads it pairs
+// with), then the pass's cap and the hap's two (BC, nb) candidates.
+HapClasses classify_haps(const Local& loc, const Scan& sc, const Settings& cfg, int n_cu, PlanScratch& S,
+                         PhaseTimer& tm)
+{
+    const int64_t nr = loc.nr, nh = loc.nh;
+    const int32_t* hlen = sc.hlen;
+    const int pol = cfg.kernel;
     const bool use_lane = pol != 2;
-    const int seg_max_h = lane_seg_policy() == 0 ? 0 : 64 * kSegMaxBC;
-    // class: 0 seg, 1 one-lane, 2 diag W16, 3 diag W64
+    const int seg_max_h = cfg.lane_seg == 0 ? 0 : 64 * kSegMaxBC;
     grow(S.hcls, size_t(nh));
     uint8_t* hcls = S.hcls.data();
     std::atomic<int64_t> wide_a{0};
     std::atomic<int> hmax_a{0};
     // Modelled wave instructions at each cap (plan_model.hpp), for the cap choice.
-    const double ravg = double(rows_sum.load()) / double(std::max<int64_t>(nr, 1));
+    const double ravg = double(sc.rows_sum) / double(std::max<int64_t>(nr, 1));
     std::mutex work_mu;
     std::array<int64_t, kNCaps> lanes_at{};
     std::array<double, kNCaps> work_at{};
@@ -612,11 +635,9 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
         }
     }, 4096);
     tm.mark("hap classes: cost");
-    CapChoice cc = choose_cap(lanes_at.data(), work_at.data(), dv.n_cu);
-    {
-        const int64_t forced = env_i64("HC_PHMM_SEG_CAP", 0);
-        if (forced > 0) cc = CapChoice{int(std::max<int64_t>(kSegMinBC, std::min<int64_t>(kSegMaxBC, forced))), false};
-    }
+    CapChoice cc = choose_cap(lanes_at.data(), work_at.data(), n_cu);
+    if (cfg.seg_cap > 0)
+        cc = CapChoice{int(std::max<int64_t>(kSegMinBC, std::min<int64_t>(kSegMaxBC, cfg.seg_cap))), false};
     const int cap = cc.cap;
     // A pass with few waves per SIMD is latency-bound: its time is one wave's,
     // so the candidate with the shorter wave wins there (S1: 11 lanes of 14
@@ -641,460 +662,402 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
         }
     }, 1 << 14);
     tm.mark("hap classes");
+    return HapClasses{hcls, hcand, hmax_a.load(), wide_a.load(), cap, waste};
+}
 
+// The width cap and candidate policy of a structured plan, priced over
+// its actual waves (grid_policy) at every cap: the cap model's ~60
+// filled lanes per wave misjudges haps that need more than 32 lanes
+// (one pair per wave): a 415 x 8 region took 12-column blocks, 35
+// lanes, one pair per wave, 3 320 waves (a fourth wave on a quarter
+// of the SIMDs), where 16-column blocks give two pairs per wave and
+// 1 660 waves. Returns the policy; another cap re-makes hc.hcand.
+int choose_grid_policy(const Local& loc, const Scan& sc, const HapClasses& hc, const Settings& cfg, int n_cu)
+{
+    int qgrid = cfg.seg_q;
+    if (cfg.seg_q >= 0 || !cfg.grid_policy) return qgrid;
+    const int32_t* hlen = sc.hlen;
+    Cand* hcand = hc.hcand;
+    const int n_simd = 4 * n_cu, cap = hc.cap;
+    double best = 0;
+    qgrid = grid_policy(loc, sc.rlen, [&](int64_t h) { return hcand[h]; }, hc.waste, n_simd, &best);
+    const double best_default = best;
+    int best_cap = cap;
+    if (cfg.seg_cap <= 0 && cfg.grid_caps)
+        for (int c : kCaps) {
+            if (c == cap) continue;
+            double e = 0;
+            const int q = grid_policy(loc, sc.rlen, [&](int64_t h) { return cand_of(hlen[size_t(h)], c); }, hc.waste,
+                                      n_simd, &e);
+            if (e > 0 && e < best * 0.98 && e < best_default * 0.95) {   // (another cap only for a clear gain)
+                best = e;
+                best_cap = c;
+                qgrid = q;
+            }
+        }
+    if (best_cap != cap)
+        parallel_for(loc.nh, [&](int64_t lo, int64_t hi) {
+            for (int64_t h = lo; h < hi; ++h)
+                if (hc.hcls[size_t(h)] == 0) hcand[size_t(h)] = cand_of(hlen[size_t(h)], best_cap);
+        }, 1 << 14);
+    return qgrid;
+}
+
+// What the per-pair pass finds; the classes' pair lists (seg_in, one_ord,
+// ord2) and the segmented pairs' shapes (seg_bc, seg_nb) are in the scratch.
+struct PairClasses {
+    int64_t cells;
+    int rmin, rmax;   // read lengths of the segmented pairs
+};
+
+// Per pair: descriptor straight into the staging image, class, and for
+// segmented pairs the cheaper candidate for its R; then the stable split of
+// the pairs by class.
+PairClasses classify_pairs(const Local& loc, const Scan& sc, const HapClasses& hc, const Settings& cfg, PairDesc* pd,
+                           PlanScratch& S)
+{
+    const PartSpec& spec = *loc.spec;
+    const int64_t npairs = loc.np;
+    grow(S.cls, size_t(npairs));
+    grow(S.seg_bc, size_t(npairs));
+    grow(S.seg_nb, size_t(npairs));
+    uint8_t *cls = S.cls.data(), *seg_bc = S.seg_bc.data(), *seg_nb = S.seg_nb.data();
     std::atomic<int64_t> cells_a{0};
-    std::vector<int>&one_ord = S.one_ord, (&ord2)[2] = S.ord2;
-    std::vector<int>& seg_ord = S.seg_ord;
-    std::vector<LaneWave>& lw = S.lw;
-    lw.clear();
-    const int qforce = int(env_i64("HC_PHMM_SEG_Q", -1));   // sweeps: force the nb0 (0) or nb0 + 1 (1) candidate
-    // Cross products whose haps all take segmented waves (every region call):
-    // the structured planner (plan_grid); HC_PHMM_GRID_PLAN=0 forces the
-    // general one (A/B, tests).
-    bool grid = !spec.flat && env_i64("HC_PHMM_GRID_PLAN", 1) != 0;
-    for (int64_t h = 0; grid && h < nh; ++h) grid = hcls[size_t(h)] == 0;
-    // Structured plans outside dry runs: pair descriptors, slot order and waves
-    // are built on the device from the block and segment tables.
-    const bool dev_plan = grid && !dry;
-    GridDev& gd = S.gdev;
-    if (grid) {
-        one_ord.clear();
-        ord2[0].clear();
-        ord2[1].clear();
-        // The width cap and candidate policy of a structured plan, priced over
-        // its actual waves (grid_policy) at every cap: the cap model's ~60
-        // filled lanes per wave misjudges haps that need more than 32 lanes
-        // (one pair per wave): a 415 x 8 region took 12-column blocks, 35
-        // lanes, one pair per wave, 3 320 waves (a fourth wave on a quarter
-        // of the SIMDs), where 16-column blocks give two pairs per wave and
-        // 1 660 waves.
-        int qgrid = qforce;
-        if (qforce < 0 && env_i64("HC_PHMM_GRID_POLICY", 1) != 0) {
-            const int n_simd = 4 * dv.n_cu;
-            double best = 0;
-            qgrid = grid_policy(loc, rlen, [&](int64_t h) { return hcand[h]; }, waste, n_simd, &best);
-            const double best_default = best;
-            int best_cap = cap;
-            if (env_i64("HC_PHMM_SEG_CAP", 0) <= 0 && env_i64("HC_PHMM_GRID_CAPS", 1) != 0)
-                for (int c : kCaps) {
-                    if (c == cap) continue;
-                    double e = 0;
-                    const int q = grid_policy(loc, rlen, [&](int64_t h) { return cand_of(hlen[size_t(h)], c); }, waste,
-                                              n_simd, &e);
-                    if (e > 0 && e < best * 0.98 && e < best_default * 0.95) {   // (another cap only for a clear gain)
-                        best = e;
-                        best_cap = c;
-                        qgrid = q;
-                    }
-                }
-            if (best_cap != cap)
-                parallel_for(nh, [&](int64_t lo, int64_t hi) {
-                    for (int64_t h = lo; h < hi; ++h)
-                        if (hcls[size_t(h)] == 0) hcand[size_t(h)] = cand_of(hlen[size_t(h)], best_cap);
-                }, 1 << 14);
+    std::atomic<int> rmin_a{INT32_MAX}, rmax_a{0};
+    const float* waste = hc.waste;
+    const int qforce = cfg.seg_q;
+    const int T = int(std::min<int64_t>(64, std::max<int64_t>(1, npairs / cfg.task_pairs)));
+    const int64_t pchunk = (npairs + T - 1) / T;
+    std::vector<std::array<int64_t, 4>> tcnt(size_t(T) + 1);
+    WorkerPool::get().run(T, [&](int t) {
+        const int64_t lo = t * pchunk, hi = std::min(npairs, lo + pchunk);
+        // Plain restrict locals: the uint8_t stores below may alias anything,
+        // so anything reached through a capture would be reloaded per pair.
+        const int32_t* __restrict rl = sc.rlen;
+        const int32_t* __restrict hl = sc.hlen;
+        const int64_t* __restrict ro = sc.row_off;
+        const int64_t* __restrict hw = sc.hap_w;
+        const uint8_t* __restrict hcl = hc.hcls;
+        const Cand* __restrict cand = hc.hcand;
+        PairDesc* __restrict pdo = pd;
+        uint8_t* __restrict clo = cls;
+        uint8_t* __restrict bco = seg_bc;
+        uint8_t* __restrict nbo = seg_nb;
+        int64_t c = 0, cn0 = 0, cn1 = 0, cn2 = 0, cn3 = 0;
+        int rlo = INT32_MAX, rhi = 0;
+        auto one = [=, &c, &cn0, &cn1, &cn2, &cn3, &rlo, &rhi](int64_t k, int64_t r, int64_t h) {
+            const int R = rl[r], H = hl[h];
+            pdo[k] = PairDesc{int(ro[r]), R, int(hw[h]), H};
+            c += int64_t(R) * H;
+            const int cl = hcl[h];
+            clo[k] = uint8_t(cl);
+            if (cl == 0) {
+                ++cn0;
+                const Cand cd = cand[h];
+                // modelled wave instructions: nb lanes x (13 per column + 26 per
+                // step) x (R + nb - 1) steps, times half the lane waste of a
+                // wave of such pairs alone (floor(64 / nb) groups): uniform
+                // batches pack like that, mixed ones fill the gaps with others;
+                // with few waves, the wave's own time (per lane)
+                auto cost = [&](int q) { return seg_cost(cd.nb[q], cd.bc[q], R, waste); };
+                const int q = qforce >= 0 ? qforce : cost(1) < cost(0) ? 1 : 0;
+                bco[k] = cd.bc[q];
+                nbo[k] = cd.nb[q];
+                rlo = R < rlo ? R : rlo;
+                rhi = R > rhi ? R : rhi;
+            } else {
+                cn1 += cl == 1;
+                cn2 += cl == 2;
+                cn3 += cl == 3;
+            }
+        };
+        if (spec.flat) {
+            for (int64_t k = lo; k < hi; ++k) one(k, k, k);
+        } else {
+            loc.pairs(lo, hi, one);
         }
-        cells_a = plan_grid(loc, rlen, hlen, row_off.data(), hap_w.data(), hcand, waste, qgrid, pd, !dev_plan, seg_ord, lw,
-                            tm, dev_plan ? &gd : nullptr);
-        tm.mark("grid: pairs");
+        cells_a += c;
+        tcnt[size_t(t) + 1] = {cn0, cn1, cn2, cn3};
+        int cur = rmin_a.load();
+        while (rlo < cur && !rmin_a.compare_exchange_weak(cur, rlo)) {
+        }
+        cur = rmax_a.load();
+        while (rhi > cur && !rmax_a.compare_exchange_weak(cur, rhi)) {
+        }
+    });
+    // Stable split of the pairs by class (per-task offsets, parallel scatter).
+    std::array<int64_t, 4> cls_tot{};
+    for (int t = 1; t <= T; ++t)
+        for (int q = 0; q < 4; ++q) {
+            const int64_t v = tcnt[size_t(t)][size_t(q)];
+            tcnt[size_t(t)][size_t(q)] = cls_tot[size_t(q)];
+            cls_tot[size_t(q)] += v;
+        }
+    S.seg_in.resize(size_t(cls_tot[0]));
+    S.one_ord.resize(size_t(cls_tot[1]));
+    S.ord2[0].resize(size_t(cls_tot[2]));
+    S.ord2[1].resize(size_t(cls_tot[3]));
+    WorkerPool::get().run(T, [&](int t) {
+        int* dst[4] = {S.seg_in.data(), S.one_ord.data(), S.ord2[0].data(), S.ord2[1].data()};
+        int64_t pos[4];
+        for (int q = 0; q < 4; ++q) pos[q] = tcnt[size_t(t) + 1][size_t(q)];
+        for (int64_t k = t * pchunk, e = std::min(npairs, k + pchunk); k < e; ++k) {
+            const int q = cls[size_t(k)];
+            dst[q][pos[q]++] = int(k);
+        }
+    });
+    return PairClasses{cells_a.load(), rmin_a.load(), rmax_a.load()};
+}
+
+// Sorted by (BC, steps = R + nb - 1) descending: a wave runs the most
+// steps of its pairs, and one width holds nb from 2 to about 10, so by
+// (BC, R) the groups of few lanes finished early and idled (0.011 of
+// S2's swept lane-cells). nb <= 64 widens the key range.
+void sort_seg_pairs(const PairClasses& pc, const PairDesc* pd, int64_t npairs, PlanScratch& S)
+{
+    std::vector<int>& seg_in = S.seg_in;
+    if (seg_in.empty()) return;
+    const uint8_t *seg_bc = S.seg_bc.data(), *seg_nb = S.seg_nb.data();
+    const int rlo = pc.rmin, sspan = pc.rmax - rlo + 64;
+    const int nbk = (kSegMaxBC / 2 + 1) * sspan;
+    if (nbk <= (1 << 18)) {
+        counting_sort_desc(seg_in, S.sort_tmp, S.hist, nbk, [&](int p) {
+            return (seg_bc[size_t(p)] / 2) * sspan + (pd[p].y - rlo + seg_nb[size_t(p)] - 1);
+        });
     } else {
-        // Per pair: descriptor straight into the staging image, class, and for
-        // segmented pairs the cheaper candidate for its R.
-        grow(S.cls, size_t(npairs));
-        grow(S.seg_bc, size_t(npairs));
-        grow(S.seg_nb, size_t(npairs));
-        uint8_t *cls = S.cls.data(), *seg_bc = S.seg_bc.data(), *seg_nb = S.seg_nb.data();
-        std::atomic<int> rmin_a{INT32_MAX}, rmax_a{0};
-        // Pairs per planning task (a 415 x 128 region call on the GPU box: 2.0 ms
-        // at 8192, 2.96 ms on one task; tools/region_ab.py).
-        const int64_t task_pairs = std::max<int64_t>(1024, env_i64("HC_PHMM_TASK_PAIRS", 8192));
-        const int T = int(std::min<int64_t>(64, std::max<int64_t>(1, npairs / task_pairs)));
-        const int64_t pchunk = (npairs + T - 1) / T;
-        std::vector<std::array<int64_t, 4>> tcnt(size_t(T) + 1);
-        WorkerPool::get().run(T, [&](int t) {
-            const int64_t lo = t * pchunk, hi = std::min(npairs, lo + pchunk);
-            // Plain restrict locals: the uint8_t stores below may alias anything,
-            // so anything reached through a capture would be reloaded per pair.
-            const int32_t* __restrict rl = rlen;
-            const int32_t* __restrict hl = hlen;
-            const int64_t* __restrict ro = row_off.data();
-            const int64_t* __restrict hw = hap_w.data();
-            const uint8_t* __restrict hc = hcls;
-            const Cand* __restrict cand = hcand;
-            PairDesc* __restrict pdo = pd;
-            uint8_t* __restrict clo = cls;
-            uint8_t* __restrict bco = seg_bc;
-            uint8_t* __restrict nbo = seg_nb;
-            int64_t c = 0, cn0 = 0, cn1 = 0, cn2 = 0, cn3 = 0;
-            int rlo = INT32_MAX, rhi = 0;
-            auto one = [=, &c, &cn0, &cn1, &cn2, &cn3, &rlo, &rhi](int64_t k, int64_t r, int64_t h) {
-                const int R = rl[r], H = hl[h];
-                pdo[k] = PairDesc{int(ro[r]), R, int(hw[h]), H};
-                c += int64_t(R) * H;
-                const int cl = hc[h];
-                clo[k] = uint8_t(cl);
-                if (cl == 0) {
-                    ++cn0;
-                    const Cand cd = cand[h];
-                    // modelled wave instructions: nb lanes x (13 per column + 26 per
-                    // step) x (R + nb - 1) steps, times half the lane waste of a
-                    // wave of such pairs alone (floor(64 / nb) groups): uniform
-                    // batches pack like that, mixed ones fill the gaps with others;
-                    // with few waves, the wave's own time (per lane)
-                    auto cost = [&](int q) { return seg_cost(cd.nb[q], cd.bc[q], R, waste); };
-                    const int q = qforce >= 0 ? qforce : cost(1) < cost(0) ? 1 : 0;
-                    bco[k] = cd.bc[q];
-                    nbo[k] = cd.nb[q];
-                    rlo = R < rlo ? R : rlo;
-                    rhi = R > rhi ? R : rhi;
-                } else {
-                    cn1 += cl == 1;
-                    cn2 += cl == 2;
-                    cn3 += cl == 3;
-                }
-            };
-            if (spec.flat) {
-                for (int64_t k = lo; k < hi; ++k) one(k, k, k);
-            } else {
-                loc.pairs(lo, hi, one);
-            }
-            cells_a += c;
-            tcnt[size_t(t) + 1] = {cn0, cn1, cn2, cn3};
-            int cur = rmin_a.load();
-            while (rlo < cur && !rmin_a.compare_exchange_weak(cur, rlo)) {
-            }
-            cur = rmax_a.load();
-            while (rhi > cur && !rmax_a.compare_exchange_weak(cur, rhi)) {
-            }
-        });
-        // Stable split of the pairs by class (per-task offsets, parallel scatter).
-        std::array<int64_t, 4> cls_tot{};
-        for (int t = 1; t <= T; ++t)
-            for (int q = 0; q < 4; ++q) {
-                const int64_t v = tcnt[size_t(t)][size_t(q)];
-                tcnt[size_t(t)][size_t(q)] = cls_tot[size_t(q)];
-                cls_tot[size_t(q)] += v;
-            }
-        std::vector<int>& seg_in = S.seg_in;
-        seg_in.resize(size_t(cls_tot[0]));
-        one_ord.resize(size_t(cls_tot[1]));
-        ord2[0].resize(size_t(cls_tot[2]));
-        ord2[1].resize(size_t(cls_tot[3]));
-        WorkerPool::get().run(T, [&](int t) {
-            int* dst[4] = {seg_in.data(), one_ord.data(), ord2[0].data(), ord2[1].data()};
-            int64_t pos[4];
-            for (int q = 0; q < 4; ++q) pos[q] = tcnt[size_t(t) + 1][size_t(q)];
-            for (int64_t k = t * pchunk, e = std::min(npairs, k + pchunk); k < e; ++k) {
-                const int q = cls[size_t(k)];
-                dst[q][pos[q]++] = int(k);
-            }
-        });
-        tm.mark("pairs");
-        // Sorted by (BC, steps = R + nb - 1) descending: a wave runs the most
-        // steps of its pairs, and one width holds nb from 2 to about 10, so by
-        // (BC, R) the groups of few lanes finished early and idled (0.011 of
-        // S2's swept lane-cells). nb <= 64 widens the key range.
-        if (!seg_in.empty()) {
-            const int rlo = rmin_a.load(), sspan = rmax_a.load() - rlo + 64;
-            const int nbk = (kSegMaxBC / 2 + 1) * sspan;
-            if (nbk <= (1 << 18)) {
-                counting_sort_desc(seg_in, S.sort_tmp, S.hist, nbk, [&](int p) {
-                    return (seg_bc[size_t(p)] / 2) * sspan + (pd[p].y - rlo + seg_nb[size_t(p)] - 1);
-                });
-            } else {
-                std::vector<uint32_t>& key = S.key;
-                grow(key, size_t(npairs));
-                for (int p : seg_in)
-                    key[size_t(p)] = (uint32_t(seg_bc[size_t(p)]) << 16) |
-                                     uint32_t(std::min(pd[p].y + seg_nb[size_t(p)] - 1, 65535));
-                sort_desc(seg_in, key);
-            }
-        }
-        tm.mark("seg sort");
-        // Packing in independent segments of the sorted list (one per task; a
-        // segment boundary costs at most one partly filled wave).
-        const int64_t ns = int64_t(seg_in.size());
-        seg_ord.resize(size_t(ns));
-        {
-            const int T = int(std::min<int64_t>(64, std::max<int64_t>(1, ns / task_pairs)));
-            const int64_t chunk = (ns + T - 1) / T;
-            std::vector<std::vector<LaneWave>>& part_w = S.part_w;
-            if (part_w.size() < size_t(T)) part_w.resize(size_t(T));
-            for (auto& W : part_w) W.clear();
-            S.used.assign(size_t(ns), 0);
-            // The packing reads (BC, nb, R) of the pairs in sorted order: gather
-            // them once into a sequential array (one parallel pass of random
-            // reads, instead of three per look-ahead probe on one task per 16k
-            // pairs: 0.3 ms of a 415 x 128 region's planning on the GPU box).
-            std::vector<uint32_t>& srec = S.srec;
-            grow(srec, size_t(ns));
-            parallel_for(ns, [&](int64_t lo, int64_t hi) {
-                for (int64_t k = lo; k < hi; ++k) {
-                    const int p = seg_in[size_t(k)];
-                    srec[size_t(k)] = uint32_t(seg_bc[size_t(p)]) | uint32_t(seg_nb[size_t(p)]) << 8 |
-                                      uint32_t(std::min(pd[p].y, 65535)) << 16;
-                }
-            });
-            // Smallest nb of each width in the part: a wave whose free lanes drop
-            // below it cannot take another pair of its width, so its look-ahead
-            // stops there (a uniform region once scanned all 64 entries per wave).
-            std::array<uint8_t, kSegMaxBC + 1> minnb;
-            minnb.fill(64);
-            for (int64_t k = 0; k < ns; ++k) {
-                uint8_t& m = minnb[srec[size_t(k)] & 0xff];
-                m = std::min<uint8_t>(m, uint8_t(srec[size_t(k)] >> 8));
-            }
-            WorkerPool::get().run(T, [&](int t) {
-                const int64_t b = t * chunk, e = std::min(ns, b + chunk);
-                if (b >= e) return;
-                const int64_t m = e - b;
-                const int* __restrict in = seg_in.data() + b;
-                const uint32_t* __restrict rec = srec.data() + b;
-                int* __restrict ordo = seg_ord.data();
-                uint8_t* __restrict used = S.used.data() + b;
-                auto& W = part_w[size_t(t)];
-                int64_t slot_n = b;
-                constexpr int64_t kLook = 64;
-                // Knapsack over the free lanes: best[kLook + c] is the largest
-                // sum of nb * steps of the items seen so far on at most c lanes
-                // (entries below kLook stand for c < 0), take[k][c] whether
-                // item k raised it. Fixed trip counts, so the loops vectorise.
-                constexpr int32_t kNever = -(1 << 30);
-                int32_t bufa[2 * kLook], bufb[2 * kLook];
-                std::fill(bufa, bufa + kLook, kNever);
-                std::fill(bufb, bufb + kLook, kNever);
-                uint8_t take[kLook][kLook];
-                int item_j[kLook], item_nb[kLook];
-                for (int64_t i = 0; i < m; ++i) {
-                    if (used[i]) continue;
-                    const int bc = int(rec[i] & 0xff);
-                    LaneWave w{};
-                    w.slot0 = int(slot_n);
-                    w.ncols = bc;
-                    int rmin = INT32_MAX, rmax = 0, nst = 0, np = 0;
-                    auto put = [&](int64_t j) {
-                        const uint32_t r = rec[j];
-                        const int nb = int((r >> 8) & 0xff), R = int(r >> 16);
-                        used[j] = 1;
-                        ordo[slot_n++] = in[j];
-                        ++np;
-                        rmax = R > rmax ? R : rmax;
-                        rmin = R < rmin ? R : rmin;
-                        nst = R + nb - 1 > nst ? R + nb - 1 : nst;
-                    };
-                    // The first unused pair opens the wave: no later entry of
-                    // the sorted list runs more steps, so none lengthens it.
-                    put(i);
-                    const int cap = 64 - int((rec[i] >> 8) & 0xff);
-                    if (cap >= minnb[size_t(bc)]) {
-                        // Of the unused pairs of this width in the window, the
-                        // subset on at most cap lanes with the largest sum of
-                        // nb * steps: in effect full lanes first, then the longest pairs.
-                        // Only the first cap / nb pairs of one nb can matter.
-                        uint8_t seen[kLook + 1] = {};
-                        int32_t* cur = bufa + kLook;
-                        int32_t* nxt = bufb + kLook;
-                        std::fill(cur, cur + kLook, 0);
-                        int n = 0;
-                        const int64_t jend = std::min(m, i + kLook);
-                        for (int64_t j = i + 1; j < jend; ++j) {
-                            if (used[j]) continue;
-                            const uint32_t r = rec[j];
-                            if (int(r & 0xff) != bc) break;
-                            const int nb = int((r >> 8) & 0xff);
-                            if (nb > cap || (seen[nb] + 1) * nb > cap) continue;
-                            ++seen[nb];
-                            const int32_t v = int32_t(nb) * (int32_t(r >> 16) + nb - 1);
-                            const int32_t* __restrict from = cur - nb;
-                            const int32_t* __restrict keep = cur;
-                            int32_t* __restrict to = nxt;
-                            uint8_t* __restrict tk = take[n];
-                            for (int c = 0; c < int(kLook); ++c) {
-                                const int32_t with = from[c] + v;
-                                const bool t = with > keep[c];   // ties stay with the earlier pairs
-                                tk[c] = t;
-                                to[c] = t ? with : keep[c];
-                            }
-                            std::swap(cur, nxt);
-                            item_j[n] = int(j - i);
-                            item_nb[n] = nb;
-                            ++n;
-                            // No later pair runs more steps than this one, so
-                            // they add at most `steps` per lane still free:
-                            // once no fill can pass best[cap] that way, the
-                            // rest of the window changes nothing.
-                            if (n % 4 == 0) {
-                                const int32_t steps = int32_t(r >> 16) + nb - 1;
-                                const int32_t* __restrict at = cur;
-                                int32_t bound = 0;
-                                for (int c = 0; c <= cap; ++c) {
-                                    const int32_t x = at[c] + (cap - c) * steps;
-                                    bound = x > bound ? x : bound;
-                                }
-                                if (bound <= cur[cap]) break;
-                            }
-                        }
-                        int c = cap, nsel = 0, sel[kLook];
-                        for (int k = n - 1; k >= 0; --k)
-                            if (take[k][c]) {
-                                sel[nsel++] = item_j[k];
-                                c -= item_nb[k];
-                            }
-                        for (int k = nsel - 1; k >= 0; --k) put(i + sel[k]);
-                    }
-                    w.npairs = np;
-                    w.rmax = rmax;
-                    w.rmin = rmin;
-                    w.nsteps = nst;
-                    W.push_back(w);
-                }
-            });
-            size_t nw = 0;
-            for (auto& W : part_w) nw += W.size();
-            lw.reserve(nw);
-            for (auto& W : part_w) lw.insert(lw.end(), W.begin(), W.end());
-        }
-    }
-    tm.mark("seg pack: fill");
-    // Dispatch order: the bulk in packing order (co-resident waves share one
-    // width's code), the shortest waves filling the last tail_rounds rounds of
-    // wave slots last, longest first (LPT, duration ~ BC * nsteps), so the chip
-    // drains evenly. Waves address their pairs through slot0: no pair moves.
-    {
-        // Structured (region) plans keep their order: their waves are in width
-        // then read-length order already, and the reorder measured slower there
-        // (415 x 128 region: fp32 0.937 -> 0.908 ms without it, call 1.43 -> 1.30 ms,
-        // profiles/r02_region_dev_sweep.jsonl).
-        const int64_t tail_rounds = std::max<int64_t>(0, env_i64("HC_PHMM_TAIL_ROUNDS", grid ? 0 : 2));
-        const size_t nw = lw.size();
-        const size_t K = std::min(nw, size_t(tail_rounds) * 4 * size_t(dv.n_cu) * kSegWavesPerSimd);
-        std::vector<int64_t>& wc = S.wcost;
-        wc.resize(nw);
-        int64_t cmin = INT64_MAX, cmax = 0;
-        for (size_t k = 0; k < nw; ++k) {
-            wc[k] = int64_t(lw[k].ncols) * lw[k].nsteps;
-            cmin = std::min(cmin, wc[k]);
-            cmax = std::max(cmax, wc[k]);
-        }
-        // Waves of (nearly) equal length (one region's cross product) drain
-        // evenly in any order: no reorder.
-        if (K > 0 && K < nw && cmax * 20 > cmin * 21) {
-            // Keys (cost, index) in one word each: the K shortest by one
-            // nth_element, then those longest first, ties in packing order.
-            std::vector<uint64_t>& key = S.wkey;
-            key.resize(nw);
-            for (size_t k = 0; k < nw; ++k) key[k] = uint64_t(wc[k]) << 32 | k;
-            std::nth_element(key.begin(), key.begin() + long(K), key.end());
-            for (size_t k = 0; k < K; ++k) key[k] = uint64_t(cmax - int64_t(key[k] >> 32)) << 32 | (key[k] & 0xffffffffu);
-            std::sort(key.begin(), key.begin() + long(K));
-            std::vector<uint8_t>& in_tail = S.in_tail;
-            in_tail.assign(nw, 0);
-            for (size_t k = 0; k < K; ++k) in_tail[key[k] & 0xffffffffu] = 1;
-            std::vector<LaneWave>& ordered = S.ordered;
-            ordered.clear();
-            ordered.reserve(nw);
-            for (size_t k = 0; k < nw; ++k)
-                if (!in_tail[k]) ordered.push_back(lw[k]);
-            for (size_t k = 0; k < K; ++k) ordered.push_back(lw[key[k] & 0xffffffffu]);
-            lw.swap(ordered);
-        }
-        // (A snake order over the SIMDs for one-round plans, heaviest wave
-        // beside the lightest, cut S4's busiest-SIMD modelled sum from 1.30x
-        // the mean to 1.10x but not the pass, 0.278 vs 0.274 ms: two waves of
-        // this pass on one SIMD are latency-bound. Removed)
-    }
-    tm.mark("seg pack");
-    const int n_seg_waves = dev_plan ? int(gd.waves) : int(lw.size());
-    const int n_seg_slots = dev_plan ? int(gd.slots) : int(seg_ord.size());
-    // One lane per pair with the carry buffer (haps longer than the segmented
-    // kernel's reach, or policy "off"): binned by (H rounded up to 16, R).
-    const int lane_var = lane_variant_id();
-    const LaneVariant& LV = lane_variant(lane_var);
-    int64_t carry_rows = 0;
-    {
         std::vector<uint32_t>& key = S.key;
         grow(key, size_t(npairs));
-        auto cols16 = [&](int p) { return (pd[p].w + 15) / 16 * 16; };
-        for (int p : one_ord) key[size_t(p)] = (uint32_t(cols16(p)) << 16) | uint32_t(std::min(pd[p].y, 65535));
-        sort_desc(one_ord, key);
-        const size_t per_wave = size_t(64) * LV.P;
-        for (size_t s0 = 0; s0 < one_ord.size(); s0 += per_wave) {
-            LaneWave w{};
-            w.slot0 = n_seg_slots + int(s0);
-            w.rmin = INT32_MAX;
-            for (size_t k = s0; k < std::min(one_ord.size(), s0 + per_wave); ++k) {
-                const int p = one_ord[k];
-                w.rmax = std::max(w.rmax, pd[p].y);
-                w.rmin = std::min(w.rmin, pd[p].y);
-                w.ncols = std::max(w.ncols, cols16(p));
-            }
-            w.carry_row = carry_rows;
-            if (w.ncols > LV.BC) carry_rows += w.rmax + 1;
-            lw.push_back(w);
-        }
-        // Anti-diagonal classes: W by H; (stripes, H) descending so the G pairs
-        // sharing a wave have equal stripe counts and similar H, heaviest first.
-        const int Wc[2] = {16, 64};
-        for (int c = 0; c < 2; ++c) {
-            for (int p : ord2[c]) key[size_t(p)] = (uint32_t((pd[p].y + Wc[c] - 1) / Wc[c]) << 16) | uint32_t(pd[p].w);
-            sort_desc(ord2[c], key);
-        }
+        for (int p : seg_in)
+            key[size_t(p)] = (uint32_t(seg_bc[size_t(p)]) << 16) |
+                             uint32_t(std::min(pd[p].y + seg_nb[size_t(p)] - 1, 65535));
+        sort_desc(seg_in, key);
     }
-    tm.mark("one-lane/diag bins");
+}
 
-    // Staging fill: order, wave list, read descriptors + bytes, hap bytes.
-    int* ordp = reinterpret_cast<int*>(host + o_ord);
+// Packing in independent segments of the sorted list (one per task; a
+// segment boundary costs at most one partly filled wave): seg_in -> the slot
+// order seg_ord and the waves lw (appended).
+void pack_seg_waves(const PairDesc* pd, int64_t task_pairs, PlanScratch& S)
+{
+    const std::vector<int>& seg_in = S.seg_in;
+    const uint8_t *seg_bc = S.seg_bc.data(), *seg_nb = S.seg_nb.data();
+    const int64_t ns = int64_t(seg_in.size());
+    S.seg_ord.resize(size_t(ns));
+    const int T = int(std::min<int64_t>(64, std::max<int64_t>(1, ns / task_pairs)));
+    const int64_t chunk = (ns + T - 1) / T;
+    std::vector<std::vector<LaneWave>>& part_w = S.part_w;
+    if (part_w.size() < size_t(T)) part_w.resize(size_t(T));
+    for (auto& W : part_w) W.clear();
+    S.used.assign(size_t(ns), 0);
+    // The packing reads (BC, nb, R) of the pairs in sorted order: gather
+    // them once into a sequential array (one parallel pass of random
+    // reads, instead of three per look-ahead probe on one task per 16k
+    // pairs: 0.3 ms of a 415 x 128 region's planning on the GPU box).
+    std::vector<uint32_t>& srec = S.srec;
+    grow(srec, size_t(ns));
+    parallel_for(ns, [&](int64_t lo, int64_t hi) {
+        for (int64_t k = lo; k < hi; ++k) {
+            const int p = seg_in[size_t(k)];
+            srec[size_t(k)] = uint32_t(seg_bc[size_t(p)]) | uint32_t(seg_nb[size_t(p)]) << 8 |
+                              uint32_t(std::min(pd[p].y, 65535)) << 16;
+        }
+    });
+    // Smallest nb of each width in the part: a wave whose free lanes drop
+    // below it cannot take another pair of its width, so its look-ahead
+    // stops there (a uniform region once scanned all 64 entries per wave).
+    std::array<uint8_t, kSegMaxBC + 1> minnb;
+    minnb.fill(64);
+    for (int64_t k = 0; k < ns; ++k) {
+        uint8_t& m = minnb[srec[size_t(k)] & 0xff];
+        m = std::min<uint8_t>(m, uint8_t(srec[size_t(k)] >> 8));
+    }
+    WorkerPool::get().run(T, [&](int t) {
+        const int64_t b = t * chunk, e = std::min(ns, b + chunk);
+        if (b >= e) return;
+        pack_segment(srec.data() + b, seg_in.data() + b, e - b, minnb.data(), S.used.data() + b, S.seg_ord.data(), b,
+                     part_w[size_t(t)]);
+    });
+    size_t nw = 0;
+    for (auto& W : part_w) nw += W.size();
+    S.lw.reserve(nw);
+    for (auto& W : part_w) S.lw.insert(S.lw.end(), W.begin(), W.end());
+}
+
+// The general planner: every pair's descriptor, class and shape, the
+// segmented pairs sorted and packed into waves. Returns the batch's cells.
+int64_t plan_general(const Local& loc, const Scan& sc, const HapClasses& hc, const Settings& cfg, PairDesc* pd,
+                     PlanScratch& S, PhaseTimer& tm)
+{
+    const PairClasses pc = classify_pairs(loc, sc, hc, cfg, pd, S);
+    tm.mark("pairs");
+    sort_seg_pairs(pc, pd, loc.np, S);
+    tm.mark("seg sort");
+    pack_seg_waves(pd, cfg.task_pairs, S);
+    return pc.cells;
+}
+
+// Dispatch order: the bulk in packing order (co-resident waves share one
+// width's code), the shortest waves filling the last tail_rounds rounds of
+// wave slots last, longest first (LPT, duration ~ BC * nsteps), so the chip
+// drains evenly. Waves address their pairs through slot0: no pair moves.
+void reorder_tail(std::vector<LaneWave>& lw, bool grid, const Settings& cfg, int n_cu, PlanScratch& S)
+{
+    // Structured (region) plans keep their order: their waves are in width
+    // then read-length order already, and the reorder measured slower there
+    // (415 x 128 region: fp32 0.937 -> 0.908 ms without it, call 1.43 -> 1.30 ms,
+    // profiles/r02_region_dev_sweep.jsonl).
+    const int64_t tail_rounds =
+        std::max<int64_t>(0, cfg.tail_rounds != INT64_MIN ? cfg.tail_rounds : grid ? 0 : 2);
+    const size_t nw = lw.size();
+    const size_t K = std::min(nw, size_t(tail_rounds) * 4 * size_t(n_cu) * kSegWavesPerSimd);
+    std::vector<int64_t>& wc = S.wcost;
+    wc.resize(nw);
+    int64_t cmin = INT64_MAX, cmax = 0;
+    for (size_t k = 0; k < nw; ++k) {
+        wc[k] = int64_t(lw[k].ncols) * lw[k].nsteps;
+        cmin = std::min(cmin, wc[k]);
+        cmax = std::max(cmax, wc[k]);
+    }
+    // Waves of (nearly) equal length (one region's cross product) drain
+    // evenly in any order: no reorder.
+    if (K > 0 && K < nw && cmax * 20 > cmin * 21) {
+        // Keys (cost, index) in one word each: the K shortest by one
+        // nth_element, then those longest first, ties in packing order.
+        std::vector<uint64_t>& key = S.wkey;
+        key.resize(nw);
+        for (size_t k = 0; k < nw; ++k) key[k] = uint64_t(wc[k]) << 32 | k;
+        std::nth_element(key.begin(), key.begin() + long(K), key.end());
+        for (size_t k = 0; k < K; ++k) key[k] = uint64_t(cmax - int64_t(key[k] >> 32)) << 32 | (key[k] & 0xffffffffu);
+        std::sort(key.begin(), key.begin() + long(K));
+        std::vector<uint8_t>& in_tail = S.in_tail;
+        in_tail.assign(nw, 0);
+        for (size_t k = 0; k < K; ++k) in_tail[key[k] & 0xffffffffu] = 1;
+        std::vector<LaneWave>& ordered = S.ordered;
+        ordered.clear();
+        ordered.reserve(nw);
+        for (size_t k = 0; k < nw; ++k)
+            if (!in_tail[k]) ordered.push_back(lw[k]);
+        for (size_t k = 0; k < K; ++k) ordered.push_back(lw[key[k] & 0xffffffffu]);
+        lw.swap(ordered);
+    }
+    // (A snake order over the SIMDs for one-round plans, heaviest wave
+    // beside the lightest, cut S4's busiest-SIMD modelled sum from 1.30x
+    // the mean to 1.10x but not the pass, 0.278 vs 0.274 ms: two waves of
+    // this pass on one SIMD are latency-bound. Removed)
+}
+
+// One lane per pair with the carry buffer (haps longer than the segmented
+// kernel's reach, or policy "off"): binned by (H rounded up to 16, R), their
+// waves appended to lw; then the anti-diagonal classes' orders. Returns the
+// carry rows the one-lane waves need.
+int64_t bin_lane_and_diag(const PairDesc* pd, int64_t npairs, int n_seg_slots, const LaneVariant& LV, PlanScratch& S)
+{
+    std::vector<int>& one_ord = S.one_ord;
+    int64_t carry_rows = 0;
+    std::vector<uint32_t>& key = S.key;
+    grow(key, size_t(npairs));
+    auto cols16 = [&](int p) { return (pd[p].w + 15) / 16 * 16; };
+    for (int p : one_ord) key[size_t(p)] = (uint32_t(cols16(p)) << 16) | uint32_t(std::min(pd[p].y, 65535));
+    sort_desc(one_ord, key);
+    const size_t per_wave = size_t(64) * LV.P;
+    for (size_t s0 = 0; s0 < one_ord.size(); s0 += per_wave) {
+        LaneWave w{};
+        w.slot0 = n_seg_slots + int(s0);
+        w.rmin = INT32_MAX;
+        for (size_t k = s0; k < std::min(one_ord.size(), s0 + per_wave); ++k) {
+            const int p = one_ord[k];
+            w.rmax = std::max(w.rmax, pd[p].y);
+            w.rmin = std::min(w.rmin, pd[p].y);
+            w.ncols = std::max(w.ncols, cols16(p));
+        }
+        w.carry_row = carry_rows;
+        if (w.ncols > LV.BC) carry_rows += w.rmax + 1;
+        S.lw.push_back(w);
+    }
+    // Anti-diagonal classes: W by H; (stripes, H) descending so the G pairs
+    // sharing a wave have equal stripe counts and similar H, heaviest first.
+    for (int c = 0; c < 2; ++c) {
+        const int W = kDiagW[c];
+        for (int p : S.ord2[c]) key[size_t(p)] = (uint32_t((pd[p].y + W - 1) / W) << 16) | uint32_t(pd[p].w);
+        sort_desc(S.ord2[c], key);
+    }
+    return carry_rows;
+}
+
+// The counts of a finished plan (a structured plan's are its device tables').
+struct Counts {
+    int n_seg_waves, n_seg_slots;
+    int64_t carry_rows;
+    int lane_variant;
+};
+
+// What travels of the staging image: [up0, up_mid) and, for structured plans,
+// [o_bases, o_lw) and the block and segment tables [o_gb, upload).
+struct Image {
+    bool dev_plan;
+    size_t upload, up0, up_mid, o_gb, o_gs, o_gr, o_gh;
+    size_t o_ord0;   // order entries ahead of the anti-diagonal classes'
+};
+
+// Staging fill: order, wave list, read descriptors + bytes, hap bytes.
+Image fill_staging(const Local& loc, const Scan& sc, const UploadLayout& U, char* host, bool dev_plan,
+                   const Counts& n, int64_t fill_grain, const PlanScratch& S)
+{
+    const Src& src = *loc.src;
+    const PartSpec& spec = *loc.spec;
+    const std::vector<int>&seg_ord = S.seg_ord, &one_ord = S.one_ord, (&ord2)[2] = S.ord2;
+    const std::vector<LaneWave>& lw = S.lw;
+    const GridDev& gd = S.gdev;
+    Image im{};
+    im.dev_plan = dev_plan;
+    int* ordp = reinterpret_cast<int*>(host + U.o_ord);
     std::memcpy(ordp, seg_ord.data(), sizeof(int) * seg_ord.size());
-    std::memcpy(ordp + n_seg_slots, one_ord.data(), sizeof(int) * one_ord.size());
-    const size_t o_ord0 = size_t(n_seg_slots) + one_ord.size();
-    std::memcpy(ordp + o_ord0, ord2[0].data(), sizeof(int) * ord2[0].size());
-    std::memcpy(ordp + o_ord0 + ord2[0].size(), ord2[1].data(), sizeof(int) * ord2[1].size());
+    std::memcpy(ordp + n.n_seg_slots, one_ord.data(), sizeof(int) * one_ord.size());
+    im.o_ord0 = size_t(n.n_seg_slots) + one_ord.size();
+    std::memcpy(ordp + im.o_ord0, ord2[0].data(), sizeof(int) * ord2[0].size());
+    std::memcpy(ordp + im.o_ord0 + ord2[0].size(), ord2[1].data(), sizeof(int) * ord2[1].size());
     if (!dev_plan) {   // structured plans build it on the device (grid_waves)
-        int* so = reinterpret_cast<int*>(host + o_slotof);
-        parallel_for(npairs, [&](int64_t lo, int64_t hi) { std::fill(so + lo, so + hi, -1); }, 1 << 16);
+        int* so = reinterpret_cast<int*>(host + U.o_slotof);
+        parallel_for(loc.np, [&](int64_t lo, int64_t hi) { std::fill(so + lo, so + hi, -1); }, 1 << 16);
         parallel_for(int64_t(seg_ord.size()), [&](int64_t lo, int64_t hi) {
             for (int64_t k = lo; k < hi; ++k) so[seg_ord[size_t(k)]] = int(k);
         }, 1 << 16);
     }
-    std::memcpy(host + o_lw, lw.data(), sizeof(LaneWave) * lw.size());
-    size_t upload = o_lw + sizeof(LaneWave) * (dev_plan ? size_t(n_seg_waves) : lw.size());
+    std::memcpy(host + U.o_lw, lw.data(), sizeof(LaneWave) * lw.size());
+    im.upload = U.o_lw + sizeof(LaneWave) * (dev_plan ? size_t(n.n_seg_waves) : lw.size());
     // Structured plans: the pair descriptors, the slot order and the waves are
     // built on the device (launch_grid_pairs, launch_grid_waves), so the upload
     // skips them and carries the block and segment tables instead.
-    const bool dev_pairs = dev_plan;
-    const size_t up0 = dev_pairs ? o_rd : 0;
-    const size_t up_mid = dev_plan ? o_ord : upload;   // [up0, up_mid) and [o_gb, upload) travel
-    size_t o_gb = 0, o_gs = 0, o_gr = 0, o_gh = 0;
-    if (dev_pairs) {
-        o_gb = (upload + 15) & ~size_t(15);
-        GridBlock* gb = reinterpret_cast<GridBlock*>(host + o_gb);
+    im.up0 = dev_plan ? U.o_rd : 0;
+    im.up_mid = dev_plan ? U.o_ord : im.upload;
+    if (dev_plan) {
+        im.o_gb = (im.upload + 15) & ~size_t(15);
+        GridBlock* gb = reinterpret_cast<GridBlock*>(host + im.o_gb);
         for (size_t b = 0; b < spec.blocks.size(); ++b)
             gb[b] = GridBlock{loc.blk_p[b], spec.blocks[b].nr, spec.blocks[b].nh, int(loc.blk_r[b]), int(loc.blk_h[b])};
-        o_gs = (o_gb + sizeof(GridBlock) * spec.blocks.size() + 15) & ~size_t(15);
-        std::memcpy(host + o_gs, gd.segs.data(), sizeof(GridSeg) * gd.segs.size());
-        o_gr = (o_gs + sizeof(GridSeg) * gd.segs.size() + 15) & ~size_t(15);
-        std::memcpy(host + o_gr, gd.rord.data(), sizeof(int) * gd.rord.size());
-        o_gh = (o_gr + sizeof(int) * gd.rord.size() + 15) & ~size_t(15);
-        std::memcpy(host + o_gh, gd.hord.data(), sizeof(int) * gd.hord.size());
-        upload = o_gh + sizeof(int) * gd.hord.size();
+        im.o_gs = (im.o_gb + sizeof(GridBlock) * spec.blocks.size() + 15) & ~size_t(15);
+        std::memcpy(host + im.o_gs, gd.segs.data(), sizeof(GridSeg) * gd.segs.size());
+        im.o_gr = (im.o_gs + sizeof(GridSeg) * gd.segs.size() + 15) & ~size_t(15);
+        std::memcpy(host + im.o_gr, gd.rord.data(), sizeof(int) * gd.rord.size());
+        im.o_gh = (im.o_gr + sizeof(int) * gd.rord.size() + 15) & ~size_t(15);
+        std::memcpy(host + im.o_gh, gd.hord.data(), sizeof(int) * gd.hord.size());
+        im.upload = im.o_gh + sizeof(int) * gd.hord.size();
     }
-    // Reads (haps) per staging task: a region's few hundred reads go on this
-    // thread alone below HC_PHMM_FILL_GRAIN (a pool wake-up cost about what
-    // the packing of 415 reads does).
-    const int64_t fill_grain = std::max<int64_t>(1, env_i64("HC_PHMM_FILL_GRAIN", 256));
-    int4* rdesc = reinterpret_cast<int4*>(host + o_rd);
-    uint8_t* hb = reinterpret_cast<uint8_t*>(host + o_bases);
-    uint8_t* hq = reinterpret_cast<uint8_t*>(host + o_quals);
-    uint8_t* hg = reinterpret_cast<uint8_t*>(host + o_gaps);
-    parallel_for(nr, [&](int64_t b, int64_t e) {
+    int4* rdesc = reinterpret_cast<int4*>(host + U.o_rd);
+    uint8_t* hb = reinterpret_cast<uint8_t*>(host + U.o_bases);
+    uint8_t* hq = reinterpret_cast<uint8_t*>(host + U.o_quals);
+    uint8_t* hg = reinterpret_cast<uint8_t*>(host + U.o_gaps);
+    const size_t gap_stride = U.gap_stride;
+    parallel_for(loc.nr, [&](int64_t b, int64_t e) {
         for (int64_t r = b; r < e; ++r) {
             const ReadView v = src.read(loc.read_id(r));
-            const size_t o = size_t(row_off[size_t(r)]);
+            const size_t o = size_t(sc.row_off[size_t(r)]);
             pack_nibbles(v.bases, v.len, hb + o / 2);
             std::memcpy(hq + o, v.q, size_t(v.len));
-            const int32_t g = gapw[size_t(r)];
+            const int32_t g = sc.gapw[size_t(r)];
             int go = 0;
             if (g < 0) {
-                go = int(gap_off[size_t(r)]);
+                go = int(sc.gap_off[size_t(r)]);
                 std::memcpy(hg + go, v.i, size_t(v.len));
                 std::memcpy(hg + gap_stride + size_t(go), v.d, size_t(v.len));
                 std::memcpy(hg + 2 * gap_stride + size_t(go), v.c, size_t(v.len));
@@ -1102,244 +1065,307 @@ int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool
             rdesc[r] = make_int4(int(o), v.len, g, go);
         }
     }, fill_grain);
-    int4* hdesc = reinterpret_cast<int4*>(host + o_hd);
-    uint8_t* hbytes = reinterpret_cast<uint8_t*>(host + o_hb);
-    parallel_for(nh, [&](int64_t b, int64_t e) {
+    int4* hdesc = reinterpret_cast<int4*>(host + U.o_hd);
+    uint8_t* hbytes = reinterpret_cast<uint8_t*>(host + U.o_hb);
+    parallel_for(loc.nh, [&](int64_t b, int64_t e) {
         for (int64_t h = b; h < e; ++h) {
             const HapView v = src.hapv(loc.hap_id(h));
-            pack_nibbles(v.bases, v.len, hbytes + hap_b[size_t(h)]);
-            hdesc[h] = make_int4(int(hap_b[size_t(h)]), v.len, int(hap_w[size_t(h)]), 0);
+            pack_nibbles(v.bases, v.len, hbytes + sc.hap_b[size_t(h)]);
+            hdesc[h] = make_int4(int(sc.hap_b[size_t(h)]), v.len, int(sc.hap_w[size_t(h)]), 0);
         }
     }, fill_grain);
-    tm.mark("staging fill");
-    if (dry) {
-        // Dry runs keep the last part's plan for the host-logic tests
-        // (hcx_dump_*): pair descriptors, slot order, segmented waves.
-        std::lock_guard<std::mutex> lk(g_dump.mu);
-        g_dump.pairs.assign(pd, pd + npairs);
-        g_dump.order.assign(seg_ord.begin(), seg_ord.end());
-        g_dump.order.insert(g_dump.order.end(), one_ord.begin(), one_ord.end());
-        g_dump.waves.assign(lw.begin(), lw.begin() + n_seg_waves);
-        g_dump.n_seg_slots = n_seg_slots;
-        g_dump.grid = grid;
-        *out = nullptr;
-        return HC_PHMM_OK;
-    }
+    return im;
+}
 
-    // Device region: the upload image, then packed rows / tables, outputs, scratch.
+// Dry runs keep the last part's plan for the host-logic tests
+// (hcx_dump_*): pair descriptors, slot order, segmented waves.
+void keep_dry_dump(const PairDesc* pd, int64_t npairs, const Counts& n, bool grid, const PlanScratch& S)
+{
+    std::lock_guard<std::mutex> lk(g_dump.mu);
+    g_dump.pairs.assign(pd, pd + npairs);
+    g_dump.order.assign(S.seg_ord.begin(), S.seg_ord.end());
+    g_dump.order.insert(g_dump.order.end(), S.one_ord.begin(), S.one_ord.end());
+    g_dump.waves.assign(S.lw.begin(), S.lw.begin() + n.n_seg_waves);
+    g_dump.n_seg_slots = n.n_seg_slots;
+    g_dump.grid = grid;
+}
+
+// Offsets of what follows the upload image in the part's device allocation.
+struct DevLayout {
+    size_t o_rows, o_hapw, o_carry, o_ring, ring_bytes, total;
+    RescueLayout R;
+    int cls_ring[2];
+    int wide_ring_blocks;
+};
+
+// Device region: the upload image, then packed rows / tables, outputs, scratch.
+int device_layout(const Local& loc, const Scan& sc, const HapClasses& hc, const Image& im, const PairDesc* pd,
+                  const Counts& n, int lane_pairs, const PlanScratch& S, DevLayout& D)
+{
+    const size_t hap_words = size_t(sc.hap_w[size_t(loc.nh)]);
     Layout L;
-    L.off = (upload + 255) & ~size_t(255);
-    // Packed rows with slack on both sides: the segmented kernels prefetch
-    // read words PD steps ahead without clamping to the read (run_seg), so a
-    // lane in pipeline fill reads up to 64 words before its read and a pair
-    // shorter than its wave's longest read up to that length + 64 past it;
-    // those words only feed rows that are never used.
-    const size_t row_pad = kRowPadBefore + size_t(rlen_max.load()) + 256;
-    if (int64_t(nrows) + int64_t(row_pad) > kMaxRowWords)
-        return fail(HC_PHMM_EINVAL, "batch too large (read bases of one part exceed 2^30)");
-    if (int64_t(hap_w[size_t(nh)]) + 16 > kMaxHapWords)
-        return fail(HC_PHMM_EINVAL, "batch too large (hap match tables of one part exceed 2^30 words)");
-    const size_t o_rows = L.take(sizeof(uint32_t) * (size_t(nrows) + row_pad));
-    const size_t o_hapw = L.take(sizeof(uint32_t) * (size_t(hap_w[size_t(nh)]) + 16));
-    const size_t o_res = L.take(res_bytes);
-    const size_t o_rec = L.take(sizeof(uint4) * std::max<size_t>(size_t(n_seg_slots), 1));   // seg slot records
-    const size_t o_sdesc = L.take(sizeof(PairDesc) * std::max<size_t>(size_t(n_seg_slots), 1));   // slot -> descriptor
-    const size_t o_list = L.take(2 * sizeof(int) * n1);   // pair ids, then pack_rh (Seg64Args::list_rh)
-    const size_t o_sorted = L.take(sizeof(int) * n1);
-    const size_t o_worder = L.take(sizeof(int) * n1);
-    const size_t o_big = L.take(sizeof(int) * n1);
-    const size_t o_bigc = L.take(sizeof(int));
-    const size_t o_plan = L.take(sizeof(Seg64Plan));
-    const size_t o_carry = L.take(sizeof(float2) * size_t(carry_rows) * 64 * LV.P);
+    L.off = (im.upload + 255) & ~size_t(255);
+    const size_t row_pad = row_pad_words(sc.rlen_max);
+    if (const int rc = check_pool_words(sc.nrows, row_pad, int64_t(hap_words))) return rc;
+    D.o_rows = L.take(sizeof(uint32_t) * (size_t(sc.nrows) + row_pad));
+    D.o_hapw = L.take(sizeof(uint32_t) * (hap_words + 16));
+    D.R = take_rescue(L, size_t(std::max<int64_t>(loc.np, 1)), size_t(n.n_seg_slots));
+    D.o_carry = L.take(sizeof(float2) * size_t(n.carry_rows) * 64 * lane_pairs);
     // Anti-diagonal stripe rings too long for the LDS (kernels.hpp
     // diag_ring_in_lds) live in global memory, one slice per workgroup; the
     // fp32 classes and the fp64 wide-hap pass run one after another and share it.
-    const int Wc[2] = {16, 64};
-    int cls_ring[2] = {0, 0};
     size_t ring_bytes = 0;
     for (int c = 0; c < 2; ++c) {
+        const int W = kDiagW[c];
         int hm = 0;
-        for (int p : ord2[c]) hm = std::max(hm, pd[p].w);
-        cls_ring[c] = hm + 2 * Wc[c] + 16;
-        if (!ord2[c].empty() && !diag_ring_in_lds(Wc[c], cls_ring[c], false)) {
-            const size_t G = size_t(64 / Wc[c]);
-            const size_t blocks = std::min<size_t>((ord2[c].size() + G - 1) / G, kDiagRingBlocks);
-            ring_bytes = std::max(ring_bytes, blocks * G * size_t(cls_ring[c]) * sizeof(float2));
+        for (int p : S.ord2[c]) hm = std::max(hm, pd[p].w);
+        D.cls_ring[c] = hm + 2 * W + 16;
+        if (!S.ord2[c].empty() && !diag_ring_in_lds(W, D.cls_ring[c], false)) {
+            const size_t G = size_t(64 / W);
+            const size_t blocks = std::min<size_t>((S.ord2[c].size() + G - 1) / G, kDiagRingBlocks);
+            ring_bytes = std::max(ring_bytes, blocks * G * size_t(D.cls_ring[c]) * sizeof(float2));
         }
     }
-    const int Hmax = hmax_a.load();
     // The fp64 wide pass runs only for rescued wide pairs (usually none or a
     // few), so its global ring is sized for kWideRing64Blocks workgroups (each
     // loops over its share of the list), not for every wide pair: a call with
     // a thousand 262k-base haps would otherwise reserve ~4 GB, kept by its slot
     // (advisor round 3).
-    int wide_ring_blocks = 0;
-    if (wide_a.load() > 0 && !diag_ring_in_lds(64, Hmax + 2 * 64 + 16, true)) {
-        wide_ring_blocks = int(std::min<int64_t>(wide_a.load(), kWideRing64Blocks));
-        ring_bytes = std::max(ring_bytes, size_t(wide_ring_blocks) * size_t(Hmax + 2 * 64 + 16) * 2 * sizeof(double));
+    D.wide_ring_blocks = 0;
+    if (hc.n_wide > 0 && !diag_ring_in_lds(64, hc.hmax + 2 * 64 + 16, true)) {
+        D.wide_ring_blocks = int(std::min<int64_t>(hc.n_wide, kWideRing64Blocks));
+        ring_bytes = std::max(ring_bytes, size_t(D.wide_ring_blocks) * size_t(hc.hmax + 2 * 64 + 16) * 2 * sizeof(double));
     }
-    const size_t o_ring = L.take(ring_bytes);
-    const size_t total = L.off;
+    D.ring_bytes = ring_bytes;
+    D.o_ring = L.take(ring_bytes);
+    D.total = L.off;
+    return HC_PHMM_OK;
+}
 
-    auto* b = new_part(&dv);
-    PartGuard guard(b);   // error returns and exceptions discard it (the caller returns the slot)
-    b->slot = slot;
-    b->spec = spec;
+// The part's device memory (its slot's, or an allocation of its own: dev_base
+// is set as soon as that exists, so discarding the part frees it), every
+// device pointer and count of the Part, and its streams.
+int bind_part(Part* b, Device& dv, Slot* slot, char* host, const Local& loc, const UploadLayout& U, const Image& im,
+              const DevLayout& D, const HapClasses& hc, const Counts& n, int64_t cells, const PlanScratch& S)
+{
     char* dev = nullptr;
     int rc = HC_PHMM_OK;
     if (slot) {
-        rc = slot_reserve(*slot, total, 0);
+        rc = slot_reserve(*slot, D.total, 0);
         dev = slot->dev;
-    } else if (hipMalloc(&dev, total) != hipSuccess) {
-        rc = fail(HC_PHMM_ENOMEM, "device allocation failed (" + std::to_string(total >> 20) + " MiB)");
+    } else if (hipMalloc(&dev, D.total) != hipSuccess) {
+        rc = fail(HC_PHMM_ENOMEM, "device allocation failed (" + std::to_string(D.total >> 20) + " MiB)");
     }
     if (rc) return rc;
     b->dev_base = dev;
-    b->n = npairs;
-    b->cells = cells_a.load();
-    b->Hmax = Hmax;
-    b->n_lane = int(size_t(n_seg_slots) + one_ord.size());
-    b->n_seg_waves = n_seg_waves;
-    b->lane_variant = lane_var;
-    b->lane_waves = dev_plan ? n_seg_waves : int(lw.size());
-    b->upload_bytes = dev_pairs ? (up_mid - up0) + (o_lw - o_bases) + (upload - o_gb) : upload - up0;
-    b->d_pairs = reinterpret_cast<PairDesc*>(dev + o_pairs);
-    b->d_rows = reinterpret_cast<uint32_t*>(dev + o_rows) + kRowPadBefore;
-    b->d_hapw = reinterpret_cast<uint32_t*>(dev + o_hapw);
-    int* d_ord = reinterpret_cast<int*>(dev + o_ord);
+    b->n = loc.np;
+    b->cells = cells;
+    b->Hmax = hc.hmax;
+    b->n_lane = int(size_t(n.n_seg_slots) + S.one_ord.size());
+    b->n_seg_waves = n.n_seg_waves;
+    b->lane_variant = n.lane_variant;
+    b->lane_waves = im.dev_plan ? n.n_seg_waves : int(S.lw.size());
+    b->upload_bytes = im.dev_plan ? (im.up_mid - im.up0) + (U.o_lw - U.o_bases) + (im.upload - im.o_gb) : im.upload - im.up0;
+    b->d_pairs = reinterpret_cast<PairDesc*>(dev + U.o_pairs);
+    b->d_rows = reinterpret_cast<uint32_t*>(dev + D.o_rows) + kRowPadBefore;
+    b->d_hapw = reinterpret_cast<uint32_t*>(dev + D.o_hapw);
+    int* d_ord = reinterpret_cast<int*>(dev + U.o_ord);
     b->d_lane_order = d_ord;
-    b->cls[0].d_order = d_ord + o_ord0;
-    b->cls[1].d_order = d_ord + o_ord0 + ord2[0].size();
+    b->cls[0].d_order = d_ord + im.o_ord0;
+    b->cls[1].d_order = d_ord + im.o_ord0 + S.ord2[0].size();
     for (int c = 0; c < 2; ++c) {
-        b->cls[c].W = Wc[c];
-        b->cls[c].n = int(ord2[c].size());
-        b->cls[c].ring_len = cls_ring[c];
+        b->cls[c].W = kDiagW[c];
+        b->cls[c].n = int(S.ord2[c].size());
+        b->cls[c].ring_len = D.cls_ring[c];
     }
-    b->d_ring = ring_bytes ? dev + o_ring : nullptr;
-    b->d_lane_waves = reinterpret_cast<LaneWave*>(dev + o_lw);
-    b->res_bytes = res_bytes;
-    b->res_o64 = RL.o64;
-    b->res_ofl = RL.ofl;
-    b->res_ocnt = RL.ocnt;
-    b->own_raw32 = b->d_raw32 = reinterpret_cast<float*>(dev + o_res);
-    b->own_raw64 = b->d_raw64 = reinterpret_cast<double*>(dev + o_res + RL.o64);
-    b->own_flag = b->d_flag = reinterpret_cast<uint8_t*>(dev + o_res + RL.ofl);
-    b->d_list = reinterpret_cast<int*>(dev + o_list);
-    b->d_count = reinterpret_cast<int*>(dev + o_res + RL.ocnt);   // run counters (kNumCounters): the results block's tail
-    b->d_sorted = reinterpret_cast<int*>(dev + o_sorted);
-    b->d_worder = reinterpret_cast<int*>(dev + o_worder);
-    b->d_big = reinterpret_cast<int*>(dev + o_big);
-    b->d_big_count = reinterpret_cast<int*>(dev + o_bigc);
-    b->d_plan = reinterpret_cast<Seg64Plan*>(dev + o_plan);
-    b->d_rec = n_seg_slots > 0 ? reinterpret_cast<uint4*>(dev + o_rec) : nullptr;
-    b->d_slot_of = reinterpret_cast<int*>(dev + o_slotof);
-    b->d_sdesc = reinterpret_cast<PairDesc*>(dev + o_sdesc);
-    b->n_wide = wide_a.load();
-    b->wide_ring_blocks = wide_ring_blocks;
-    b->d_carry = carry_rows ? reinterpret_cast<float2*>(dev + o_carry) : nullptr;
-    if (slot) b->host_res = host + host_res_off;
+    b->d_ring = D.ring_bytes ? dev + D.o_ring : nullptr;
+    b->d_lane_waves = reinterpret_cast<LaneWave*>(dev + U.o_lw);
+    bind_rescue(*b, dev, D.R, size_t(n.n_seg_slots));
+    b->d_slot_of = reinterpret_cast<int*>(dev + U.o_slotof);
+    b->n_wide = hc.n_wide;
+    b->wide_ring_blocks = D.wide_ring_blocks;
+    b->d_carry = n.carry_rows ? reinterpret_cast<float2*>(dev + D.o_carry) : nullptr;
+    if (slot) b->host_res = host + U.res_off;
+    bind_streams(*b, dv, slot);
+    return HC_PHMM_OK;
+}
 
-    if (slot) {
-        b->stream = slot->stream;
-        b->side = slot->side;
-        b->fork = slot->fork;
-        b->join = slot->join;
-        b->slot_ev = true;
-        b->pack_ev[0] = slot->ev[0];
-        b->pack_ev[1] = slot->ev[1];
-        b->ev_pool.push_back({slot->ev[2], slot->ev[3], slot->ev[4]});
-        b->done = slot->ev[5];
-        b->early = slot->ev[6];
-    } else {
-        b->stream = dv.stream;
-        b->side = dv.side;
-        b->fork = dv.fork;
-        b->join = dv.join;
+// The device packer's view of the upload image at `img` (the part's device
+// copy, or the pinned staging image itself).
+void pack_sources(PackArgs& pack, const char* img, const UploadLayout& U)
+{
+    pack.bases = reinterpret_cast<const uint8_t*>(img + U.o_bases);
+    pack.quals = reinterpret_cast<const uint8_t*>(img + U.o_quals);
+    pack.gaps = reinterpret_cast<const uint8_t*>(img + U.o_gaps);
+    pack.rdesc = reinterpret_cast<const int4*>(img + U.o_rd);
+    pack.hap_bytes = reinterpret_cast<const uint8_t*>(img + U.o_hb);
+    pack.hdesc = reinterpret_cast<const int4*>(img + U.o_hd);
+}
+
+// Structured plans. [o_rd, o_ord): read / hap descriptors; the order and waves
+// between are built on the device; then the read / hap bytes and the block
+// and segment tables. One fused launch prepares everything.
+int enqueue_structured(Part* b, PackArgs pack, const Local& loc, const UploadLayout& U, const Image& im, char* host,
+                       const GridDev& gd, const Counts& n, int64_t zero_copy_max)
+{
+    char* dev = b->dev_base;
+    hipStream_t s = b->stream;
+    // Zero copy (a part whose upload is at most HC_PHMM_ZERO_COPY_MAX
+    // bytes, default 4 MiB: one region): the prep launch reads the
+    // pinned staging image itself over PCIe — it is the only reader of
+    // those bytes — instead of three DMA copies ahead of it.
+    char* src = dev;
+    const int64_t up_bytes = int64_t(im.up_mid - im.up0) + int64_t(U.o_lw - U.o_bases) + int64_t(im.upload - im.o_gb);
+    if (b->slot && up_bytes <= zero_copy_max) {
+        void* hp = nullptr;
+        if (hipHostGetDevicePointer(&hp, host, 0) == hipSuccess && hp) src = static_cast<char*>(hp);
     }
+    if (src == dev) {
+        HIP_TRY(hipMemcpyAsync(dev + im.up0, host + im.up0, im.up_mid - im.up0, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dev + U.o_bases, host + U.o_bases, U.o_lw - U.o_bases, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dev + im.o_gb, host + im.o_gb, im.upload - im.o_gb, hipMemcpyHostToDevice, s));
+    } else {
+        pack_sources(pack, src, U);
+    }
+    HIP_TRY(hipEventRecord(b->pack_ev[0], s));
+    GridPrepArgs g{};
+    g.pack = pack;
+    g.blocks = reinterpret_cast<const GridBlock*>(src + im.o_gb);
+    g.nblocks = int(loc.spec->blocks.size());
+    g.npairs = (long long)loc.np;
+    g.pairs = b->d_pairs;
+    g.segs = reinterpret_cast<const GridSeg*>(src + im.o_gs);
+    g.nsegs = int(gd.segs.size());
+    g.nslots = (long long)n.n_seg_slots;
+    g.nwaves = n.n_seg_waves;
+    g.rord = reinterpret_cast<const int*>(src + im.o_gr);
+    g.hord = reinterpret_cast<const int*>(src + im.o_gh);
+    g.order = b->d_lane_order;
+    g.slot_of = b->d_slot_of;
+    g.sdesc = b->d_sdesc;
+    g.waves = b->d_lane_waves;
+    g.counters = b->d_count;
+    HIP_TRY(launch_prepare_grid(g, s));
+    HIP_TRY(hipEventRecord(b->pack_ev[1], s));
+    return HC_PHMM_OK;
+}
+
+// General plans: the whole image in one copy, then the device packing.
+int enqueue_general(Part* b, const PackArgs& pack, const Image& im, const char* host)
+{
+    hipStream_t s = b->stream;
+    HIP_TRY(hipMemcpyAsync(b->dev_base + im.up0, host + im.up0, im.upload - im.up0, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(b->d_count, 0, kNumCounters * sizeof(int), s));
+    HIP_TRY(hipEventRecord(b->pack_ev[0], s));
+    HIP_TRY(launch_pack_batch(pack, s));
+    HIP_TRY(hipEventRecord(b->pack_ev[1], s));
+    return HC_PHMM_OK;
+}
+
+// The H2D and the device packing on the part's stream, then (with_run) the
+// device pass and the return of the results.
+int enqueue_upload(Part* b, const Local& loc, const UploadLayout& U, const Image& im, const Staging& st,
+                   const GridDev& gd, const Counts& n, const Settings& cfg, bool with_run)
+{
     hipStream_t s = b->stream;
     PackArgs pack{};
-    pack.bases = reinterpret_cast<const uint8_t*>(dev + o_bases);
-    pack.quals = reinterpret_cast<const uint8_t*>(dev + o_quals);
-    pack.gaps = reinterpret_cast<const uint8_t*>(dev + o_gaps);
-    pack.gap_stride = (long long)gap_stride;
-    pack.rdesc = reinterpret_cast<const int4*>(dev + o_rd);
-    pack.nreads = int(nr);
+    pack_sources(pack, b->dev_base, U);
+    pack.gap_stride = (long long)U.gap_stride;
+    pack.nreads = int(loc.nr);
     pack.rows = b->d_rows;
-    pack.hap_bytes = reinterpret_cast<const uint8_t*>(dev + o_hb);
-    pack.hdesc = reinterpret_cast<const int4*>(dev + o_hd);
-    pack.nhaps = int(nh);
+    pack.nhaps = int(loc.nh);
     pack.hapw = b->d_hapw;
     pack.pairs = b->d_pairs;
-    pack.order = d_ord;
-    pack.nslots = dev_pairs ? 0 : n_seg_slots;   // structured plans: grid_waves writes them
+    pack.order = b->d_lane_order;
+    pack.nslots = im.dev_plan ? 0 : n.n_seg_slots;   // structured plans: grid_waves writes them
     pack.sdesc = b->d_sdesc;
-    auto enqueue = [&]() -> int {
-        if (!b->slot_ev)
-            for (auto& e : b->pack_ev) HIP_TRY(hipEventCreate(&e));
-        if (dev_pairs) {
-            // [o_rd, o_ord): read / hap descriptors; the order and waves between
-            // are built on the device; then the read / hap bytes and the block
-            // and segment tables. One fused launch prepares everything.
-            // Zero copy (a part whose upload is at most HC_PHMM_ZERO_COPY_MAX
-            // bytes, default 4 MiB: one region): the prep launch reads the
-            // pinned staging image itself over PCIe — it is the only reader of
-            // those bytes — instead of three DMA copies ahead of it.
-            char* src = dev;
-            const int64_t up_bytes = int64_t(up_mid - up0) + int64_t(o_lw - o_bases) + int64_t(upload - o_gb);
-            if (slot && up_bytes <= env_i64("HC_PHMM_ZERO_COPY_MAX", int64_t(4) << 20)) {
-                void* hp = nullptr;
-                if (hipHostGetDevicePointer(&hp, host, 0) == hipSuccess && hp) src = static_cast<char*>(hp);
-            }
-            if (src == dev) {
-                HIP_TRY(hipMemcpyAsync(dev + up0, host + up0, up_mid - up0, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(dev + o_bases, host + o_bases, o_lw - o_bases, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(dev + o_gb, host + o_gb, upload - o_gb, hipMemcpyHostToDevice, s));
-            } else {
-                pack.bases = reinterpret_cast<const uint8_t*>(src + o_bases);
-                pack.quals = reinterpret_cast<const uint8_t*>(src + o_quals);
-                pack.gaps = reinterpret_cast<const uint8_t*>(src + o_gaps);
-                pack.rdesc = reinterpret_cast<const int4*>(src + o_rd);
-                pack.hap_bytes = reinterpret_cast<const uint8_t*>(src + o_hb);
-                pack.hdesc = reinterpret_cast<const int4*>(src + o_hd);
-            }
-            HIP_TRY(hipEventRecord(b->pack_ev[0], s));
-            GridPrepArgs g{};
-            g.pack = pack;
-            g.blocks = reinterpret_cast<const GridBlock*>(src + o_gb);
-            g.nblocks = int(spec.blocks.size());
-            g.npairs = (long long)npairs;
-            g.pairs = b->d_pairs;
-            g.segs = reinterpret_cast<const GridSeg*>(src + o_gs);
-            g.nsegs = int(gd.segs.size());
-            g.nslots = (long long)n_seg_slots;
-            g.nwaves = n_seg_waves;
-            g.rord = reinterpret_cast<const int*>(src + o_gr);
-            g.hord = reinterpret_cast<const int*>(src + o_gh);
-            g.order = reinterpret_cast<int*>(dev + o_ord);
-            g.slot_of = b->d_slot_of;
-            g.sdesc = b->d_sdesc;
-            g.waves = reinterpret_cast<LaneWave*>(dev + o_lw);
-            g.counters = b->d_count;
-            HIP_TRY(launch_prepare_grid(g, s));
-            HIP_TRY(hipEventRecord(b->pack_ev[1], s));
-        } else {
-            HIP_TRY(hipMemcpyAsync(dev + up0, host + up0, upload - up0, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemsetAsync(b->d_count, 0, kNumCounters * sizeof(int), s));
-            HIP_TRY(hipEventRecord(b->pack_ev[0], s));
-            HIP_TRY(launch_pack_batch(pack, s));
-            HIP_TRY(hipEventRecord(b->pack_ev[1], s));
-        }
-        if (with_run) {
-            const int r = run_part(b, s);
-            if (r) return r;
-            const int e = enqueue_results(b, s);
-            if (e) return e;
-        }
-        // A part-owned staging buffer is freed on return: the copy must be done.
-        if (own_host) HIP_TRY(hipStreamSynchronize(s));
+    if (!b->slot_ev)
+        for (auto& e : b->pack_ev) HIP_TRY(hipEventCreate(&e));
+    const int rc = im.dev_plan ? enqueue_structured(b, pack, loc, U, im, st.host, gd, n, cfg.zero_copy_max)
+                               : enqueue_general(b, pack, im, st.host);
+    if (rc) return rc;
+    if (with_run) {
+        const int r = run_part(b, s);
+        if (r) return r;
+        const int e = enqueue_results(b, s);
+        if (e) return e;
+    }
+    // A part-owned staging buffer is freed on return: the copy must be done.
+    if (st.own) HIP_TRY(hipStreamSynchronize(s));
+    return HC_PHMM_OK;
+}
+
+}  // namespace
+
+// Plan one part on device d: host binning + staging, then the H2D, device
+// packing and (with_run) the device pass and the D2H of the results, all
+// enqueued on d's stream. slot == nullptr: the part owns its memory (batches).
+int plan_part(Device& dv, const Src& src, const PartSpec& spec, Slot* slot, bool with_run, PlanMode mode,
+              Part** out)
+{
+    const bool dry = mode == PlanMode::Dry;
+    PhaseTimer tm;
+    const Settings cfg;
+    Local loc(src, spec);
+    if (loc.np > (int64_t(1) << 31) - 1) return fail(HC_PHMM_EINVAL, "too many pairs for one batch");
+    PlanScratch& S = t_scr;
+
+    Scan sc;
+    if (const int rc = scan_inputs(loc, S, sc)) return rc;
+    tm.mark("reads/haps scan");
+    const UploadLayout U = upload_layout(loc, sc);
+    Staging st;   // declared ahead of the part's guard: an owned buffer is freed after the guard drained the stream
+    if (const int rc = staging_memory(U, slot, dry, st)) return rc;
+    tm.mark("staging alloc");
+    PairDesc* pd = reinterpret_cast<PairDesc*>(st.host + U.o_pairs);
+    const HapClasses hc = classify_haps(loc, sc, cfg, dv.n_cu, S, tm);
+
+    // Cross products whose haps all take segmented waves (every region call):
+    // the structured planner (plan_grid); HC_PHMM_GRID_PLAN=0 forces the
+    // general one (A/B, tests).
+    bool grid = !spec.flat && cfg.grid_plan;
+    for (int64_t h = 0; grid && h < loc.nh; ++h) grid = hc.hcls[size_t(h)] == 0;
+    // Structured plans outside dry runs: pair descriptors, slot order and waves
+    // are built on the device from the block and segment tables.
+    const bool dev_plan = grid && !dry;
+    int64_t cells = 0;
+    S.lw.clear();
+    if (grid) {
+        S.one_ord.clear();
+        S.ord2[0].clear();
+        S.ord2[1].clear();
+        const int qgrid = choose_grid_policy(loc, sc, hc, cfg, dv.n_cu);
+        cells = plan_grid(loc, sc.rlen, sc.hlen, sc.row_off, sc.hap_w, hc.hcand, hc.waste, qgrid, pd, !dev_plan,
+                          S.seg_ord, S.lw, tm, dev_plan ? &S.gdev : nullptr);
+        tm.mark("grid: pairs");
+    } else {
+        cells = plan_general(loc, sc, hc, cfg, pd, S, tm);
+    }
+    tm.mark("seg pack: fill");
+    reorder_tail(S.lw, grid, cfg, dv.n_cu, S);
+    tm.mark("seg pack");
+    Counts n{dev_plan ? int(S.gdev.waves) : int(S.lw.size()), dev_plan ? int(S.gdev.slots) : int(S.seg_ord.size()), 0,
+             cfg.lane_variant};
+    const LaneVariant& LV = lane_variant(n.lane_variant);
+    n.carry_rows = bin_lane_and_diag(pd, loc.np, n.n_seg_slots, LV, S);
+    tm.mark("one-lane/diag bins");
+
+    const Image im = fill_staging(loc, sc, U, st.host, dev_plan, n, cfg.fill_grain, S);
+    tm.mark("staging fill");
+    if (dry) {   // no HIP call so far, none to come
+        keep_dry_dump(pd, loc.np, n, grid, S);
+        *out = nullptr;
         return HC_PHMM_OK;
-    };
-    rc = enqueue();
+    }
+
+    DevLayout D;
+    if (const int rc = device_layout(loc, sc, hc, im, pd, n, LV.P, S, D)) return rc;
+    Part* b = new_part(&dv);
+    PartGuard guard(b);   // error returns and exceptions discard it (the caller returns the slot)
+    b->slot = slot;
+    b->spec = spec;
+    if (const int rc = bind_part(b, dv, slot, st.host, loc, U, im, D, hc, n, cells, S)) return rc;
+    const int rc = enqueue_upload(b, loc, U, im, st, S.gdev, n, cfg, with_run);
     tm.mark("enqueue");
     if (rc) return rc;   // the guard drains the stream and discards the part
     *out = guard.release();

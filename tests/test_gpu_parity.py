@@ -218,6 +218,40 @@ def test_cross_regions_matches_per_region_calls(engine):
         assert np.array_equal(bits(got), bits(alone))
 
 
+_UPLOAD_RUNS = {}   # test_structured_upload_branches: setting -> result bits; "ref" -> the oracle's
+
+
+@pytest.mark.parametrize("zero_copy_max", [None, "0"])
+def test_structured_upload_branches(engine, oracle_lib, monkeypatch, zero_copy_max):
+    """A structured (region) part uploads its staging image either not at all
+    (the prep launch reads the pinned image: HC_PHMM_ZERO_COPY_MAX unset, a
+    small part) or by three DMA copies (HC_PHMM_ZERO_COPY_MAX=0; otherwise only
+    calls above 4 MiB take it). One region of 5 reads x 3 haps, reads of 20 to
+    101 bases, haps of 30, 150 and 400: at least two (BC, nb) segments and a
+    partly filled wave. Both equal the oracle and each other, bit for bit."""
+    if zero_copy_max is None:
+        monkeypatch.delenv("HC_PHMM_ZERO_COPY_MAX", raising=False)
+    else:
+        monkeypatch.setenv("HC_PHMM_ZERO_COPY_MAX", zero_copy_max)
+    rng = np.random.default_rng(41)
+    haps = [W.ACGT[rng.integers(0, 4, n)].tobytes() for n in (30, 150, 400)]
+    reads = []
+    for k, n in enumerate((20, 37, 64, 88, 101)):
+        o = int(rng.integers(0, 400 - n))
+        rs = np.frombuffer(haps[2], np.uint8)[o:o + n].copy()
+        rs[rng.integers(0, n, 2)] = W.ACGT[rng.integers(0, 4, 2)]
+        q = (rng.integers(10, 41, n) + 33).astype(np.uint8).tobytes()
+        reads.append((rs.tobytes(), q, b"I" * n, b"I" * n, b"+" * n))
+    if "ref" not in _UPLOAD_RUNS:
+        flat = W.from_pairs([(r[0], r[1], r[2], r[3], r[4], h) for r in reads for h in haps])
+        _UPLOAD_RUNS["ref"] = bits(oracle_lib.pairs(flat, nthreads=4)["loglik"].reshape(5, 3)).copy()
+    got = bits(engine.cross(reads, haps)).copy()
+    assert got.shape == _UPLOAD_RUNS["ref"].shape and np.array_equal(got, _UPLOAD_RUNS["ref"])
+    for other in (v for k, v in _UPLOAD_RUNS.items() if k != "ref"):
+        assert np.array_equal(got, other)
+    _UPLOAD_RUNS[str(zero_copy_max)] = got
+
+
 def test_auto_segmentation_on_a_shard(engine, oracle_lib, monkeypatch):
     """A 125k-pair S2 shard (one rank's share of configs[3] at 8 GPUs): the
     engine column-segments every pair (ceil(H/BC) lanes per pair). Same

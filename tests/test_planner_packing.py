@@ -1,5 +1,7 @@
 """CPU: how the general host planner packs column-segmented waves (planner.cpp
-plan_part, "seg sort" and "seg pack: fill"). Pairs are sorted by (BC, steps =
+plan_general: sort_seg_pairs, then pack_seg_waves over seg_pack.hpp
+pack_segment; HC_PHMM_TRACE phases "seg sort" and "seg pack: fill"; the packing
+alone runs under the sanitizers in test_seg_pack_host.py). Pairs are sorted by (BC, steps =
 R + nb - 1) descending; the first unused pair opens a wave and fixes its step
 count, and a knapsack over the 64-entry look-ahead fills the other lanes. The
 plans are read through the dry-run hooks as test_planner.py does. Lane
