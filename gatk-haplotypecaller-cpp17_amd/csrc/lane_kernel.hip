@@ -489,7 +489,7 @@ __device__ __forceinline__ void plan_rescue(const Seg64Args& a, int n, PlanLds& 
 }
 
 // One column-segmented wave (wid) of the fp32 pass.
-__device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float* __restrict__ slut)
+__device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float* __restrict__ ptab)
 {
     // Lane id and the wave's LDS tables in forms the compiler can recompute
     // (mbcnt) or keep in SGPRs (wave-uniform): values live across the step
@@ -537,7 +537,7 @@ __device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float
     float sumM = 0.f, sumX = 0.f;
     switch (bc) {
 #define HC_SEG_CASE(W) \
-    case W: run_seg_bc<float, W>(a.lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq); break;
+    case W: run_seg_bc<float, W>(a.lut, ptab, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq); break;
         HC_SEG_WIDTHS(HC_SEG_CASE)
 #undef HC_SEG_CASE
     default: break;
@@ -574,11 +574,12 @@ __device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float
 template <int OCC>
 __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
 {
-    // Each wave fills its own copy of the prior tables: no workgroup barrier
-    // between the kernel's start and a wave's first loads, so the fill
-    // overlaps the wave's descriptor loads (small batches are one round of
-    // waves: every wave's start-up latency is on the pass's critical path).
-    __shared__ float sluts[kSegWPB][kSlutLen];
+    // Each wave fills its own copy of the prior pair table (seg_common.hpp
+    // ptab, 4 KB): no workgroup barrier between the kernel's start and a
+    // wave's first loads, so the fill overlaps the wave's descriptor loads
+    // (small batches are one round of waves: every wave's start-up latency is
+    // on the pass's critical path).
+    __shared__ __attribute__((aligned(32))) float ptabs[kSegWPB][kPtabLen];
     const int n_waves = a.n_waves_dev ? __builtin_amdgcn_readfirstlane(*a.n_waves_dev) : a.n_waves;
     const int wib = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
     const int wid = blockIdx.x * kSegWPB + wib;
@@ -593,10 +594,10 @@ __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
         c[kPlanReady + o] = 0;
     }
     if (wid >= n_waves) return;   // wave-uniform (device-planned parts launch an upper bound)
-    float* slut = sluts[wib];
-    for (int t = __lane_id(); t < kSlutLen; t += 64) slut[t] = a.lut[t];
+    float* ptab = ptabs[wib];
+    fill_ptab(ptab, a.lut, __lane_id());
     __builtin_amdgcn_wave_barrier();
-    seg_wave(a, wid, slut);
+    seg_wave(a, wid, ptab);
 }
 
 // Wave-uniform max / min of a per-lane int (once per wave).

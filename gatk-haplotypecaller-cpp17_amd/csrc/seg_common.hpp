@@ -153,6 +153,128 @@ __device__ __forceinline__ T y_next(T Ml, T Yl, T my, T yy)
         return Ml * my + Yl * yy;
 }
 
+// The fp32 constant-gap path takes its priors from LDS instead of selecting
+// them: two adjacent columns of a row take one of four (prior, prior) pairs that
+// depend only on the row's quality q and the two columns' match bits, so each
+// seg wave keeps ptab[128][4] of float2 (4 KB),
+//   ptab[q][p] = { p & 2 ? pm[q] : px[q],  p & 1 ? pm[q] : px[q] }
+// (the pair's first column is the higher bit, as in the MSB-first window), and a
+// row reads one ds_read_b64 per two columns. The address is the row's table
+// base (32-byte aligned, once per row) with the two window bits placed at bits
+// 4:3 — a shift and a v_and_or_b32, both full rate: 2 VALU slots per two columns
+// where the carry select (prior_next) takes 6, and the reads issue on the LDS
+// port beside the other waves' VALU work. The floats multiplied are the ones
+// the select picks, so the results are the same bits.
+constexpr int kPtabPairs = kQuals * 4 * 2;    // floats of the pair table
+constexpr int kPtabLen = kPtabPairs + 2 * kQuals;   // then pm[128], px[128] for the rows that keep the select
+
+typedef float float2v __attribute__((ext_vector_type(2)));
+using lds_cfloat2 = const __attribute__((address_space(3))) float2v;
+// LDS byte address of a pointer into a __shared__ array.
+__device__ __forceinline__ uint32_t lds_addr(const void* p)
+{
+    return uint32_t(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
+}
+
+// Each lane writes the rows q = lane and lane + 64 (two 16-byte stores each);
+// wave-private, so the caller needs a wave barrier only.
+__device__ __forceinline__ void fill_ptab(float* __restrict__ ptab, const float* __restrict__ lut, int lane)
+{
+#pragma unroll
+    for (int t = 0; t < kQuals / 64; ++t) {
+        const int q = lane + 64 * t;
+        const float pm = lut[kOffPm + q], px = lut[kOffPx + q];
+        float4* d = reinterpret_cast<float4*>(ptab + q * 8);
+        d[0] = make_float4(px, px, px, pm);   // patterns 00, 01
+        d[1] = make_float4(pm, px, pm, pm);   // patterns 10, 11
+        ptab[kPtabPairs + q] = pm;
+        ptab[kPtabPairs + kQuals + q] = px;
+    }
+}
+
+// Table base of a row: ptab's LDS address + 32 * q.
+__device__ __forceinline__ uint32_t ptab_row(uint32_t ptab_lds, uint32_t w) { return ptab_lds + (row_q(w) << 5); }
+
+// The priors of block columns 2p, 2p+1 (0-based) of a row with table base
+// `base` and match words m (MSB first: column c is bit 31 - (c & 31) of word c >> 5).
+template <int P>
+__device__ __forceinline__ float2 ptab_pair(uint32_t base, const uint2& m)
+{
+    constexpr int sh = 30 - 2 * (P & 15);
+    const uint32_t w = (P >> 4) ? m.y : m.x;
+    uint32_t bits;
+    if constexpr (sh >= 3)
+        bits = w >> (sh - 3);
+    else
+        bits = w << (3 - sh);
+    const float2v v = *reinterpret_cast<lds_cfloat2*>(base | (bits & 24u));
+    return make_float2(v.x, v.y);
+}
+
+// pm[q] and px[q] alone, for the rows that keep the select: the arrays behind
+// the pair table (fp32; read from the table's own rows, 32 bytes apart, the
+// lanes of a wave meet on 8 banks) or the prior tables (fp64, load_slut).
+__device__ __forceinline__ float lds_pm(const float* __restrict__ ptab, int q) { return ptab[kPtabPairs + q]; }
+__device__ __forceinline__ float lds_px(const float* __restrict__ ptab, int q) { return ptab[kPtabPairs + kQuals + q]; }
+__device__ __forceinline__ double lds_pm(const double* __restrict__ slut, int q) { return slut[kOffPm + q]; }
+__device__ __forceinline__ double lds_px(const double* __restrict__ slut, int q) { return slut[kOffPx + q]; }
+
+// Block widths that take their priors from the table. Blocks of at most 32
+// columns are what small batches run, one round of waves at one or two per
+// SIMD: there the step is short, the two dependent LDS reads between rows
+// (window, then first pair) are not covered, and the select with its shift
+// issued ahead (cell, AHEAD) is faster (S1 at 14 columns 0.0560 -> 0.0580 ms
+// with the table, S4 at 24-32 0.671 -> 0.694; profiles/r10_prior_table_ab.jsonl).
+constexpr int kPtabMinWidth = 34;
+
+// Pairs a row holds: the one its cells consume and the one in flight, read
+// three columns ahead of its first use. One pair (read one column ahead)
+// leaves the wave waiting on the LDS, three measure no better than two (S2 fp32
+// pass 7.85 / 7.75 / 7.74 ms, profiles/r10_prior_table_ab.jsonl): by then the
+// LDS array itself is the limit.
+constexpr int kPtabAhead = 2;
+
+// Column J of one row, fp32 EQ path with table priors: `cell`'s EQ arithmetic
+// in the same order. pr is a ring of D pairs: on entry to an even column
+// J = 2p it holds pairs p .. p+D-1. The column takes its successor's prior,
+// pair p's second element and last use, and then issues the read of pair p+D
+// into pair p's registers, 2D - 1 columns ahead of its first use. The first
+// scheduling barrier keeps that multiply ahead of the read (behind it, the
+// read needs registers of its own), the second lets VALU work through and
+// keeps the LDS reads where they are (hoisted to the row's start they take
+// two registers each, sunk to their use the wave waits on every one).
+template <int BC, int J, bool SUM, int D>
+__device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float M, float& Ml, float& Yl,
+                                         float2 (&pr)[D], uint32_t base, const uint2& mrow,
+                                         const RowConst<float>& k, float& sumM, float& sumX)
+{
+    if constexpr (J < BC) {
+        float Mn = M;
+        if constexpr (J + 1 < BC) {
+            const float2& q = pr[((J + 1) / 2) % D];
+            Mn = Tt[J] * (((J + 1) & 1) ? q.y : q.x);
+        }
+        if constexpr ((J & 1) == 0 && J / 2 + D < BC / 2) {
+            constexpr int kNoDs = 0x2 | 0x4 | 0x10 | 0x20 | 0x40;   // VALU, SALU and VMEM may cross; DS may not
+            __builtin_amdgcn_sched_barrier(0);
+            pr[(J / 2 + D) % D] = ptab_pair<J / 2 + D>(base, mrow);
+            __builtin_amdgcn_sched_barrier(kNoDs);
+        }
+        const float Xc = X[J];
+        if constexpr (SUM) {
+            sumM = sumM + M;
+            sumX = sumX + Xc;
+        }
+        const float Mx = M * k.mx;
+        const float Y = (J == 0) ? Yl : (Ml + Yl * k.yy);
+        Tt[J] = (M * k.mm + Xc * k.g) + Y * k.g;
+        X[J] = Mx + Xc * k.xx;
+        Ml = Mx;
+        Yl = Y;
+        cell_tab<BC, J + 1, SUM, D>(Tt, X, Mn, Ml, Yl, pr, base, mrow, k, sumM, sumX);
+    }
+}
+
 // A lane's pair: its read rows and hap match table as 32-bit offsets from the
 // part's uniform bases (one VGPR each per lane and SGPR bases, so the loads
 // take the global_load SGPR-base + VGPR-offset form and no 64-bit address
@@ -372,15 +494,26 @@ __device__ __forceinline__ void fill_window(uint2* __restrict__ mt, int lane, co
     }
 }
 
+// slut: the wave's prior tables in LDS. fp64: [ph2pr | pm | px | gapm]
+// (load_slut); fp32: the pair table ptab (fill_ptab), which the constant-gap
+// EQ path of the wide blocks (TAB) reads two columns at a time (cell_tab).
 template <typename T, int BC, bool CG, bool EQ>
 __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __restrict__ slut, const SegSteps& st,
                                         int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
                                         uint2* __restrict__ mt)
 {
     constexpr int PD = seg_prefetch<T, BC>();
+    constexpr bool TAB = std::is_same<T, float>::value && CG && EQ && BC >= kPtabMinWidth;
+    constexpr int NP = BC / 2;   // column pairs of a row (block widths are even)
+    static_assert(!TAB || BC % 2 == 0, "table priors come two columns at a time");
     const int pad = ((cx.H + BC - 1) / BC) * BC - cx.H;   // zero columns left of column 1 (block 0)
-    const int c0 = s * BC - pad;                          // this block: columns c0+1 .. c0+BC
+    int c0 = s * BC - pad;                                // this block: columns c0+1 .. c0+BC
     const int R = cx.R;
+    // The two paths of a width start alike, and the window's addresses are
+    // hoisted above the branch between them as far as they do, where they are
+    // spilled once the paths' prologues differ. A text that differs per path
+    // ends that at the first instruction.
+    asm volatile("; run_seg CG=%1" : "+v"(c0) : "n"(int(CG)));
     fill_window(mt, lane, cx, c0);
     T Tt[BC], X[BC];
 #pragma unroll
@@ -399,6 +532,15 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     RowConst<T> k;
     row_const<T>(lut, wc, row_word(cx, min(2, R) - 1), k);
     uint2 mrow = mt[k.rc * 64 + lane];
+    // TAB: ptab's LDS address, the coming row's table base and its first
+    // pair, read at the end of the step before (here: row 1's).
+    uint32_t ptab_lds = 0, base = 0;
+    float2 pr0 = make_float2(0.f, 0.f);
+    if constexpr (TAB) {
+        ptab_lds = lds_addr(slut);
+        base = ptab_row(ptab_lds, wc);
+        pr0 = ptab_pair<0>(base, mrow);
+    }
     // A pair's last block (and any lane past it) hands zeros to the lane on its
     // right, so a group's first lane needs no select: it receives Y = 0 entering
     // column 1 and T = 0 (column 0 below row 0) from its left neighbour, and
@@ -424,18 +566,22 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
         // the read: outside rows 1..R it feeds only rows no result depends on,
         // and the packed rows carry slack on both sides (engine.cpp o_rows).
         int ridx = i + PD;
-        if constexpr (CG) {   // next row's prior constants (LDS) and match words
+        // TAB takes nothing of the next row yet: its match words, table base
+        // and first pair are read at the end of the step, when the row's own
+        // window is dead and gives them its registers (read here, they cost the
+        // widest blocks the second pair in flight).
+        if constexpr (CG && !TAB) {   // next row's prior constants (LDS) and match words
             const int qo = row_q(wn), mo = row_rc(wn) * 64 + lane;
             // Order the load after the last use of wn, so the word can land in
             // wn's register (no register move, hence no wait, at the loop back edge).
             asm volatile("" : "+v"(ridx) : "v"(qo), "v"(mo));
-            pm_n = slut[kOffPm + qo];
-            px_n = slut[kOffPx + qo];
+            pm_n = lds_pm(slut, qo);
+            px_n = lds_px(slut, qo);
             m_n = mt[mo];
-        } else {
+        } else if constexpr (!CG) {
             asm volatile("" : "+v"(ridx) : "v"(wn));
         }
-        wq[P] = row_word(cx, ridx);
+        if constexpr (!TAB) wq[P] = row_word(cx, ridx);
         const T y_in = from_left(y_out);
         const T t_in = from_left(t_out);
         T sM_in = T(0), sX_in = T(0);
@@ -459,12 +605,32 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
                 sumX = s ? sX_in : T(0);
             }
             T Ml = T(0), Yl = Yl0;
-            const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);   // bit 31 of mrow.x first
-            cell<T, BC, 0, BC, SUM, EQ>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
+            if constexpr (TAB) {
+                constexpr int D = kPtabAhead;
+                float2 pr[D];
+                pr[0] = pr0;
+                for_phases<1, (D < NP ? D : NP)>([&](auto p) {
+                    pr[decltype(p)::value] = ptab_pair<decltype(p)::value>(base, mrow);
+                });
+                const float M0 = Tdiag * pr0.x;
+                cell_tab<BC, 0, SUM, D>(Tt, X, M0, Ml, Yl, pr, base, mrow, k, sumM, sumX);
+            } else {
+                const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);   // bit 31 of mrow.x first
+                cell<T, BC, 0, BC, SUM, EQ>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
+            }
             y_out = masked<AND>(y_next<EQ>(Ml, Yl, k.my, k.yy), keep);
             t_out = masked<AND>(Tt[BC - 1], keep);
         }
-        if constexpr (CG) {
+        if constexpr (TAB) {
+            // Unconditional, as below. wn's last uses are the window's slot and
+            // the table base, so the word loaded now can land in wn's register.
+            const int mo = row_rc(wn) * 64 + lane;
+            base = ptab_row(ptab_lds, wn);
+            asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base));
+            mrow = mt[mo];
+            pr0 = ptab_pair<0>(base, mrow);
+            wq[P] = row_word(cx, ridx);
+        } else if constexpr (CG) {
             // Unconditional (no register moves for a conditional update): a
             // lane before its row 1 takes row i + 1's constants too, and at
             // i = 0 those are row 1's, what it needs on its first row.

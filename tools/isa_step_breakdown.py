@@ -20,7 +20,12 @@ v_add_co, v_lshl_*, v_cndmask on an SGPR mask, f64 arithmetic, any VOP3 with
 an SGPR operand). The prior select is v_add_co_u32 (the window shift, 2 slots)
 and the e32 v_cndmask that reads its carry from VCC (1 slot; two per fp64
 cell); s_nop (the VCC write-to-read wait states) is reported per step on its
-own: it costs issue cycles of its wave, not VALU slots."""
+own: it costs issue cycles of its wave, not VALU slots. The table path of the
+fp32 EQ loops (seg_common.hpp cell_tab) has no select: per two columns one
+shift of the window word, one v_and_or_b32 that puts its two bits into the
+row's table base (priced as the other three-source forms, 2 slots) and the
+ds_read_b64 of the pair, reported as "prior table (address)" and "prior table
+(LDS read)"."""
 import collections
 import json
 import re
@@ -38,6 +43,34 @@ def writes_vcc(op, txt):
     if "_co_" in op:
         return len(args) > 1 and args[1] == "vcc"
     return (op.startswith("v_cmp") or op.startswith("s_")) and args[0].startswith("vcc")
+
+
+def operands(txt):
+    return [a.strip() for a in txt.split(None, 1)[1].split(",")] if " " in txt else []
+
+
+def table_roles(ins):
+    """Indices of the pair table's instructions in a loop: every v_and_or_b32,
+    the shift whose result it masks, and the ds_read_b64 at its address."""
+    addr, read = set(), set()
+    shift_of, addr_regs = {}, set()
+    for i, (op, t) in enumerate(ins):
+        a = operands(t)
+        if op == "v_and_or_b32":
+            addr.add(i)
+            if a[1] in shift_of:
+                addr.add(shift_of.pop(a[1]))
+            addr_regs.add(a[0])
+            continue
+        if op == "ds_read_b64" and a[1] in addr_regs:
+            read.add(i)
+            addr_regs.discard(a[1])
+        if a and op.startswith("v_"):
+            shift_of.pop(a[0], None)
+            addr_regs.discard(a[0])
+            if op in ("v_lshrrev_b32", "v_lshlrev_b32"):
+                shift_of[a[0]] = i
+    return addr, read
 
 
 def role(op, txt, vcc_is_carry=False):
@@ -135,8 +168,13 @@ def main():
         by_role = collections.Counter()
         by_slot = collections.Counter()
         carry = False
-        for op, t in ins:
+        tab_addr, tab_read = table_roles(ins)
+        for i, (op, t) in enumerate(ins):
             r = role(op, t, carry)
+            if i in tab_addr:
+                r = "prior table (address)"
+            elif i in tab_read:
+                r = "prior table (LDS read)"
             by_role[r] += 1
             by_slot[r] += slots(op, t)
             if writes_vcc(op, t):
@@ -145,6 +183,7 @@ def main():
                          s_nop_per_step=round(c["s_nop"] / steps, 2),
                          select_ops_per_step={k: round(c[k] / steps, 2) for k in
                                               ("v_add_co_u32", "v_cndmask_b32", "v_bfe_i32", "v_bitop3_b32")},
+                         table_ops_per_step={k: round(c[k] / steps, 2) for k in ("v_and_or_b32", "ds_read_b64")},
                          cndmask_e64_per_step=round(sum(1 for op, t in ins if op == "v_cndmask_b32"
                                                         and t.split()[0].endswith("_e64")) / steps, 2),
                          arith_per_step=arith / steps,
