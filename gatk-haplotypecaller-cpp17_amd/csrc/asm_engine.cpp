@@ -20,9 +20,7 @@
 
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -32,35 +30,23 @@
 #include "pool.hpp"
 #include "stage_host.hpp"
 
-namespace hcphmm {
-int primary_device();
-void asm_release();
-}
-
 using namespace hcasm;
 using namespace stage_host;
 
 namespace {
 
-std::mutex g_mu;
-hipStream_t g_stream = nullptr;
 int g_cus = 0;
 int g_clock_khz = 0;   // of wall_clock64(), for the trace
 
 Buf g_in, g_seg, g_work, g_out, g_hin{nullptr, 0, true}, g_hback{nullptr, 0, true};
 
-int ensure_init()
-{
-    const int rc = hc_phmm_init(0, -1);
-    if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
-    if (g_stream) return HC_PHMM_OK;
-    HIP_TRY(g_stream, hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, hcphmm::primary_device()));
+// Once per stream: what the launch sizes and the trace need to know of the device.
+Stage g_st({&g_in, &g_seg, &g_work, &g_out, &g_hin, &g_hback}, true, [](hipStream_t st) -> int {
+    HIP_TRY(st, hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, hcphmm::primary_device()));
     if (hipDeviceGetAttribute(&g_clock_khz, hipDeviceAttributeWallClockRate, hcphmm::primary_device()) != hipSuccess)
         g_clock_khz = 0;
-    HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
     return HC_PHMM_OK;
-}
+});
 
 // The HC_PHMM_EINVAL cases, before any device work.
 int validate(const hc_asm_region* regions, int32_t n)
@@ -209,21 +195,21 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     a.edge_pool_used = reinterpret_cast<unsigned long long*>(g_out.p + o_used);
     a.err = reinterpret_cast<int32_t*>(g_out.p + o_err);
 
-    HIP_TRY(g_stream, hipMemcpyAsync(g_in.p, h, in_bytes, hipMemcpyHostToDevice, g_stream));
-    HIP_TRY(g_stream, hipMemsetAsync(g_out.p + o_used, 0, head_bytes - o_used, g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(g_in.p, h, in_bytes, hipMemcpyHostToDevice, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemsetAsync(g_out.p + o_used, 0, head_bytes - o_used, g_st.stream));
     if (tr.on) {
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
         tr.mark("upload");
     }
-    HIP_TRY(g_stream, launch_asm_segments(a, g_stream));
-    HIP_TRY(g_stream, launch_asm_graph(a, n_slots, g_stream));
+    HIP_TRY(g_st.stream, launch_asm_segments(a, g_st.stream));
+    HIP_TRY(g_st.stream, launch_asm_graph(a, n_slots, g_st.stream));
     if (tr.on) {
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
         tr.mark("graph");
     }
     char* hb = g_hback.p;
-    HIP_TRY(g_stream, hipMemcpyAsync(hb, g_out.p, head_bytes, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(hb, g_out.p, head_bytes, hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     int32_t err[2];
     std::memcpy(err, hb + o_err, sizeof(err));
     if (err[0] != kErrNone)
@@ -233,9 +219,9 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
     std::memcpy(&used, hb + o_used, sizeof(used));
     if (used > static_cast<unsigned long long>(edge_cap)) return fail(HC_PHMM_EHIP, "assembler: edge count out of its bound");
     if (used) {
-        HIP_TRY(g_stream, hipMemcpyAsync(hb + o_edges, g_out.p + o_edges, sizeof(hc_asm_edge) * size_t(used), hipMemcpyDeviceToHost,
-                               g_stream));
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+        HIP_TRY(g_st.stream, hipMemcpyAsync(hb + o_edges, g_out.p + o_edges, sizeof(hc_asm_edge) * size_t(used), hipMemcpyDeviceToHost,
+                               g_st.stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     }
     tr.mark("readback");
 
@@ -291,36 +277,14 @@ int run(const hc_asm_region* regions, int32_t n, uint32_t flags, hc_asm_result& 
 
 extern "C" int hc_asm_assemble(const hc_asm_region* regions, int32_t n_regions, uint32_t flags, hc_asm_result** out)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
-    if (flags & ~uint32_t(HC_ASM_WANT_GRAPH)) return fail(HC_PHMM_EINVAL, "unknown hc_asm_assemble flags");
-    int rc = validate(regions, n_regions);
-    if (rc) return rc;
-    try {
-        std::unique_ptr<hc_asm_result> res(new hc_asm_result());
-        res->flags = flags;
-        if (n_regions) {
-            rc = ensure_init();
-            if (rc) return rc;
-            rc = run(regions, n_regions, flags, *res);
-            if (rc) return rc;
-        }
-        *out = res.release();
-    } catch (const std::bad_alloc&) {
-        if (g_stream) (void)hipStreamSynchronize(g_stream);
-        return fail(HC_PHMM_ENOMEM, "host allocation failed");
-    }
-    return HC_PHMM_OK;
-}
-
-void hcphmm::asm_release()
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_stream) return;
-    (void)hipStreamSynchronize(g_stream);
-    for (Buf* b : {&g_in, &g_seg, &g_work, &g_out, &g_hin, &g_hback}) drop(*b);
-    (void)hipStreamDestroy(g_stream);
-    g_stream = nullptr;
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    return call_frame(out, &g_st.stream, [&](hc_asm_result& res) -> int {
+        if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
+        if (flags & ~uint32_t(HC_ASM_WANT_GRAPH)) return fail(HC_PHMM_EINVAL, "unknown hc_asm_assemble flags");
+        if (int rc = validate(regions, n_regions)) return rc;
+        res.flags = flags;
+        if (!n_regions) return HC_PHMM_OK;
+        if (int rc = g_st.ensure_init()) return rc;
+        return run(regions, n_regions, flags, res);
+    });
 }

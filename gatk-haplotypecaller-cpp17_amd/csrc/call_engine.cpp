@@ -12,9 +12,7 @@
 // the host wall clock of the phases and the three stage calls' durations on stderr.
 #include <chrono>
 #include <cstring>
-#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -236,22 +234,13 @@ int window_of(const hc_call_result* res, int32_t window)
 extern "C" int hc_call_windows(const hc_call_window* windows, int32_t n_windows, uint32_t flags, hc_call_result** out)
 {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (n_windows < 0 || (n_windows && !windows)) return fail(HC_PHMM_EINVAL, "null windows / negative count");
-    if (flags & ~kKnownFlags) return fail(HC_PHMM_EINVAL, "unknown hc_call_windows flags");
-    int rc = validate(windows, n_windows);
-    if (rc) return rc;
-    try {
-        std::unique_ptr<hc_call_result> res(new hc_call_result());
-        res->flags = flags;
-        rc = run(windows, n_windows, flags, *res);
-        if (rc) return rc;
-        *out = res.release();
-    } catch (const std::bad_alloc&) {
-        return fail(HC_PHMM_ENOMEM, "host allocation failed");
-    }
-    return HC_PHMM_OK;
+    return call_frame(out, nullptr, [&](hc_call_result& res) -> int {
+        if (n_windows < 0 || (n_windows && !windows)) return fail(HC_PHMM_EINVAL, "null windows / negative count");
+        if (flags & ~kKnownFlags) return fail(HC_PHMM_EINVAL, "unknown hc_call_windows flags");
+        if (int rc = validate(windows, n_windows)) return rc;
+        res.flags = flags;
+        return run(windows, n_windows, flags, res);
+    });
 }
 
 extern "C" int hc_call_result_window(const hc_call_result* res, int32_t window, int32_t* status, int32_t* asm_status,

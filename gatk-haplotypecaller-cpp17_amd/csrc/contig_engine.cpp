@@ -20,9 +20,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -32,11 +30,6 @@
 #include "sam_engine.hpp"
 #include "sam_kernels.hpp"
 #include "stage_host.hpp"
-
-namespace hcphmm {
-int primary_device();
-void contig_release();
-}
 
 using namespace hccontig;
 using namespace stage_host;
@@ -60,8 +53,9 @@ struct hc_contig_result {
 
 namespace {
 
-std::mutex g_mu;
+// No stream of its own: the tiling kernels run on the parser's, under the parser's lock.
 Buf g_pos, g_win, g_picks, g_hback{nullptr, 0, true}, g_hpicks{nullptr, 0, true};
+Stage g_st({&g_pos, &g_win, &g_picks, &g_hback, &g_hpicks}, false);
 
 constexpr uint32_t kKnownFlags = HC_CONTIG_F64 | HC_CONTIG_DEFAULT_MODE | HC_CONTIG_WANT_SITE_READS | HC_CONTIG_SKIP_UNPLACED;
 
@@ -350,31 +344,23 @@ extern "C" int hc_contig_call(const uint8_t* sam, int64_t sam_len, const char* c
                               int32_t region_size, int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags,
                               hc_contig_result** out)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (sam_len < 0 || (sam_len && !sam)) return fail(HC_PHMM_EINVAL, "null sam / negative length");
-    if (!contig || !ref) return fail(HC_PHMM_EINVAL, "null contig / ref");
-    if (flags & ~kKnownFlags) return fail(HC_PHMM_EINVAL, "unknown flags");
-    if (pick_mode != HC_CONTIG_PICK_SEEDED && pick_mode != HC_CONTIG_PICK_FIRST) return fail(HC_PHMM_EINVAL, "unknown pick mode");
-    if (ref_len < 1) return fail(HC_PHMM_EINVAL, "ref_len below 1");
-    if (region_size < 1) return fail(HC_PHMM_EINVAL, "region_size below 1");
-    if (padding_size < 0 || padding_size > region_size) return fail(HC_PHMM_EINVAL, "padding_size outside 0 .. region_size");
-    if (int64_t(region_size) + 2 * int64_t(padding_size) > HC_GT_MAX_REF_LEN)
-        return fail(HC_PHMM_EINVAL, "region_size + 2 * padding_size above " + std::to_string(HC_GT_MAX_REF_LEN));
-    if ((ref_len + region_size - 1) / region_size > 0x7fffffffLL) return fail(HC_PHMM_EINVAL, "more than 2147483647 windows");
-    try {
-        std::unique_ptr<hc_contig_result> res(new hc_contig_result());
-        res->region = region_size;
-        res->padding = padding_size;
-        res->ref_len = ref_len;
-        const int rc = run(sam, sam_len, contig, ref, ref_len, seed, pick_mode, flags, *res);
-        if (rc) return rc;
-        *out = res.release();
-    } catch (const std::bad_alloc&) {
-        return fail(HC_PHMM_ENOMEM, "host allocation failed");
-    }
-    return HC_PHMM_OK;
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    return call_frame(out, nullptr, [&](hc_contig_result& res) -> int {
+        if (sam_len < 0 || (sam_len && !sam)) return fail(HC_PHMM_EINVAL, "null sam / negative length");
+        if (!contig || !ref) return fail(HC_PHMM_EINVAL, "null contig / ref");
+        if (flags & ~kKnownFlags) return fail(HC_PHMM_EINVAL, "unknown flags");
+        if (pick_mode != HC_CONTIG_PICK_SEEDED && pick_mode != HC_CONTIG_PICK_FIRST) return fail(HC_PHMM_EINVAL, "unknown pick mode");
+        if (ref_len < 1) return fail(HC_PHMM_EINVAL, "ref_len below 1");
+        if (region_size < 1) return fail(HC_PHMM_EINVAL, "region_size below 1");
+        if (padding_size < 0 || padding_size > region_size) return fail(HC_PHMM_EINVAL, "padding_size outside 0 .. region_size");
+        if (int64_t(region_size) + 2 * int64_t(padding_size) > HC_GT_MAX_REF_LEN)
+            return fail(HC_PHMM_EINVAL, "region_size + 2 * padding_size above " + std::to_string(HC_GT_MAX_REF_LEN));
+        if ((ref_len + region_size - 1) / region_size > 0x7fffffffLL) return fail(HC_PHMM_EINVAL, "more than 2147483647 windows");
+        res.region = region_size;
+        res.padding = padding_size;
+        res.ref_len = ref_len;
+        return run(sam, sam_len, contig, ref, ref_len, seed, pick_mode, flags, res);
+    });
 }
 
 extern "C" int hc_contig_result_vcf(const hc_contig_result* res, const char** text, int64_t* length, int32_t* n_windows)
@@ -437,10 +423,4 @@ extern "C" int hc_contig_result_free(hc_contig_result* res)
 {
     delete res;
     return HC_PHMM_OK;
-}
-
-void hcphmm::contig_release()
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    for (Buf* b : {&g_pos, &g_win, &g_picks, &g_hback, &g_hpicks}) drop(*b);
 }

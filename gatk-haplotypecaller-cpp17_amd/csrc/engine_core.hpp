@@ -29,13 +29,15 @@
 #include "../../include/hc_pairhmm.h"
 #include "kernels.hpp"
 
+namespace stage_host {
+void release_all();   // stage_host.cpp: every stage engine's stream and workspace
+}
+
 namespace hcphmm {
 
-// Shared with sw_engine.cpp / gt_engine.cpp.
+// Shared with the stage engines (stage_host.hpp).
 void set_last_error(const std::string& msg);
 int primary_device();   // HIP ordinal of the first device slot, -1 if not initialised
-void sw_release();      // sw_engine.cpp: drop the aligner's stream and workspace
-void gt_release();      // gt_engine.cpp: drop the genotyper's stream and buffers
 
 namespace eng {
 

@@ -32,35 +32,31 @@
 // MathUtils Jacobian table as g++ folds it at compile time (tools/gen_jacobian.py).
 #include "math_jacobian.inc"
 
-namespace hcphmm {
-int primary_device();
-void gt_release();
-}
-
 using namespace hcgt;
 using namespace stage_host;
 
 namespace {
 
-std::mutex g_mu;
-hipStream_t g_stream = nullptr;
 double* g_jac = nullptr;
 // Grow-only workspaces: sized by the input, by the site count, and the pinned image of either.
 Buf g_dev, g_dev2, g_host{nullptr, 0, true};
 
-// Runs on the engine's first device slot, made current on the calling thread.
-int ensure_init()
+// Once per stream: the Jacobian table on the device.
+int upload_jacobian(hipStream_t st)
 {
-    const int rc = hc_phmm_init(0, -1);
-    if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
-    if (g_stream) return HC_PHMM_OK;
-    HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    HIP_TRY(g_stream, hipMalloc(&g_jac, sizeof(double) * kJacobianLen));
+    HIP_TRY(st, hipMalloc(&g_jac, sizeof(double) * kJacobianLen));
     static_assert(sizeof(kMathJacobianBits) == sizeof(double) * kJacobianLen, "table length");
-    HIP_TRY(g_stream, hipMemcpy(g_jac, kMathJacobianBits, sizeof(double) * kJacobianLen, hipMemcpyHostToDevice));
+    HIP_TRY(st, hipMemcpy(g_jac, kMathJacobianBits, sizeof(double) * kJacobianLen, hipMemcpyHostToDevice));
     return HC_PHMM_OK;
 }
+
+void free_jacobian()
+{
+    if (g_jac) (void)hipFree(g_jac);
+    g_jac = nullptr;
+}
+
+Stage& g_st = hcgt_host::stage();
 
 // The one launch of the arithmetic, shared by hc_gt_genotype_sites (records,
 // keep lists and maps uploaded) and hc_gt_call_regions (written on the device).
@@ -70,7 +66,7 @@ hipError_t launch_arithmetic(GtArgs& a)
     const double table_step = 0.0001;   // JacobianLogTable::TABLE_STEP (math_utils.hpp:24)
     a.inv_step = 1.0 / table_step;      // INV_STEP (:25)
     a.log10_2 = std::log10(2.0);        // std::log10(2) (genotyper.hpp:280,321)
-    return launch_sites(a, g_stream);
+    return launch_sites(a, g_st.stream);
 }
 
 int run(const hc_gt_site* sites, int32_t n)
@@ -154,7 +150,7 @@ int run(const hc_gt_site* sites, int32_t n)
             }
         }, 1);
         const size_t end = m1 < nm ? o_L + sizeof(double) * size_t(mat_off[size_t(m1)]) : o_keep;
-        HIP_TRY(g_stream, hipMemcpyAsync(dv + sent, h + sent, end - sent, hipMemcpyHostToDevice, g_stream));
+        HIP_TRY(g_st.stream, hipMemcpyAsync(dv + sent, h + sent, end - sent, hipMemcpyHostToDevice, g_st.stream));
         sent = end;
     }
     for (int32_t s = 0; s < n; ++s) {
@@ -162,7 +158,7 @@ int run(const hc_gt_site* sites, int32_t n)
         if (x.n_keep) std::memcpy(h + o_keep + sizeof(int32_t) * size_t(ds[size_t(s)].keep_off), x.keep, sizeof(int32_t) * size_t(x.n_keep));
         std::memcpy(h + o_map + sizeof(int32_t) * size_t(ds[size_t(s)].map_off), x.hap_allele, sizeof(int32_t) * size_t(x.n_haps));
     }
-    HIP_TRY(g_stream, hipMemcpyAsync(dv + sent, h + sent, in_bytes - sent, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(dv + sent, h + sent, in_bytes - sent, hipMemcpyHostToDevice, g_st.stream));
     GtArgs a{};
     a.sites = reinterpret_cast<const GtSite*>(dv + o_sites);
     a.n = n;
@@ -173,9 +169,9 @@ int run(const hc_gt_site* sites, int32_t n)
     a.gl = reinterpret_cast<double*>(dv + o_gl);
     a.gi = reinterpret_cast<int32_t*>(dv + o_gi);
     a.gq = reinterpret_cast<int32_t*>(dv + o_gq);
-    HIP_TRY(g_stream, launch_arithmetic(a));
-    HIP_TRY(g_stream, hipMemcpyAsync(h, dv + o_gl, tail, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, launch_arithmetic(a));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(h, dv + o_gl, tail, hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     const double* gl = reinterpret_cast<const double*>(h);
     const int32_t* gi = reinterpret_cast<const int32_t*>(h + (o_gi - o_gl));
     const int32_t* gq = reinterpret_cast<const int32_t*>(h + (o_gq - o_gl));
@@ -292,10 +288,10 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
             std::memcpy(h + o.read_end + sizeof(int64_t) * size_t(pr[size_t(r)].read_off), x.read_end, sizeof(int64_t) * size_t(x.n_reads));
         }
     }
-    HIP_TRY(g_stream, hipMemcpyAsync(dv, h, o_L, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(dv, h, o_L, hipMemcpyHostToDevice, g_st.stream));
     PlanArgs p = hcgt_host::plan_args(dv, o, n, nh);
-    HIP_TRY(g_stream, launch_plan_events(p, g_stream));
-    HIP_TRY(g_stream, hipMemcpyAsync(h + h_tot, dv + o.totals, sizeof(PlanTotals), hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(g_st.stream, launch_plan_events(p, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(h + h_tot, dv + o.totals, sizeof(PlanTotals), hipMemcpyDeviceToHost, g_st.stream));
     // The matrices are staged while the events and scan kernels run.
     hcphmm::parallel_for(n, [&](int64_t lo, int64_t hi) {
         for (int64_t r = lo; r < hi; ++r) {
@@ -305,9 +301,9 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
                             sizeof(double) * size_t(x.n_reads) * size_t(x.n_haps));
         }
     }, 1);
-    if (t.L) HIP_TRY(g_stream, hipMemcpyAsync(dv + o_L, h + o_L, in_bytes - o_L, hipMemcpyHostToDevice, g_stream));
+    if (t.L) HIP_TRY(g_st.stream, hipMemcpyAsync(dv + o_L, h + o_L, in_bytes - o_L, hipMemcpyHostToDevice, g_st.stream));
     // The one counted readback: the site count sizes everything that follows.
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     PlanTotals tot;
     std::memcpy(&tot, h + h_tot, sizeof(tot));
     const int64_t ns = tot.n_sites;
@@ -336,13 +332,13 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
     p.gt_sites = reinterpret_cast<GtSite*>(d2 + o_gs);
     p.keep = reinterpret_cast<int32_t*>(d2 + o_keep);
     p.amap = reinterpret_cast<int32_t*>(d2 + o_map);
-    HIP_TRY(g_stream, launch_plan_sites(p, ns, g_stream));
+    HIP_TRY(g_st.stream, launch_plan_sites(p, ns, g_st.stream));
     GtArgs a = hcgt_host::gt_args(p, ns, reinterpret_cast<const double*>(dv + o_L), reinterpret_cast<double*>(d2 + o_al),
                                   reinterpret_cast<double*>(d2 + o_gl), reinterpret_cast<int32_t*>(d2 + o_gi),
                                   reinterpret_cast<int32_t*>(d2 + o_gq));
-    HIP_TRY(g_stream, launch_arithmetic(a));
-    HIP_TRY(g_stream, hipMemcpyAsync(h, d2, back, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, launch_arithmetic(a));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(h, d2, back, hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     std::vector<RegionView> views(static_cast<size_t>(n));
     for (int32_t r = 0; r < n; ++r) views[size_t(r)] = RegionView{regions[r].ref, regions[r].padded_begin, regions[r].n_haps};
     hcgt_host::materialise(views.data(), hap_pool.data(), reinterpret_cast<const SiteOut*>(h + o_so), ns,
@@ -356,9 +352,11 @@ int run_regions(const hc_gt_region* regions, int32_t n, Calls& out)
 
 namespace hcgt_host {
 
-std::mutex& mutex() { return g_mu; }
-int ensure_init() { return ::ensure_init(); }
-hipStream_t stream() { return g_stream; }
+Stage& stage()
+{
+    static Stage st({&g_dev, &g_dev2, &g_host}, true, upload_jacobian, free_jacobian);
+    return st;
+}
 hipError_t launch_arithmetic(hcgt::GtArgs& a) { return ::launch_arithmetic(a); }
 
 int add_region(int32_t r, const RegionFrame& f, FrameTotals& t, PlanRegion& d,
@@ -550,30 +548,21 @@ struct hc_gt_calls {
 
 extern "C" int hc_gt_genotype_sites(const hc_gt_site* sites, int32_t n_sites)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
+    std::lock_guard<std::mutex> lk(g_st.mu);
     if (n_sites < 0 || (n_sites && !sites)) return fail(HC_PHMM_EINVAL, "null sites / negative count");
-    int rc = ensure_init();
-    if (rc) return rc;
+    if (int rc = g_st.ensure_init()) return rc;
     if (n_sites == 0) return HC_PHMM_OK;
     return run(sites, n_sites);
 }
 
 extern "C" int hc_gt_call_regions(const hc_gt_region* regions, int32_t n_regions, hc_gt_calls** out)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
-    int rc = ensure_init();
-    if (rc) return rc;
-    hc_gt_calls* calls = new hc_gt_calls();
-    if (n_regions) rc = run_regions(regions, n_regions, calls->c);
-    if (rc) {
-        delete calls;
-        return rc;
-    }
-    *out = calls;
-    return HC_PHMM_OK;
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    return call_frame(out, &g_st.stream, [&](hc_gt_calls& calls) -> int {
+        if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
+        if (int rc = g_st.ensure_init()) return rc;
+        return n_regions ? run_regions(regions, n_regions, calls.c) : HC_PHMM_OK;
+    });
 }
 
 extern "C" int hc_gt_calls_sites(const hc_gt_calls* calls, const hc_gt_call_site** sites, int64_t* n)
@@ -588,17 +577,4 @@ extern "C" int hc_gt_calls_free(hc_gt_calls* calls)
 {
     delete calls;
     return HC_PHMM_OK;
-}
-
-// Called by hc_phmm_shutdown.
-void hcphmm::gt_release()
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_stream) return;
-    (void)hipStreamSynchronize(g_stream);
-    if (g_jac) (void)hipFree(g_jac);
-    g_jac = nullptr;
-    for (Buf* b : {&g_dev, &g_dev2, &g_host}) drop(*b);
-    (void)hipStreamDestroy(g_stream);
-    g_stream = nullptr;
 }

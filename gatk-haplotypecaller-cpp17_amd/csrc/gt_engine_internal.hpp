@@ -1,5 +1,5 @@
-// What gt_engine.cpp shares with region_engine.cpp: the genotyper's stream and
-// lock, the frame of a region (its checks, its PlanRegion, the running totals
+// What gt_engine.cpp shares with region_engine.cpp: the genotyper's stage (stream
+// and lock), the frame of a region (its checks, its PlanRegion, the running totals
 // and their INT32 bound), the haplotype checks and the CIGAR parser, PlanArgs
 // and GtArgs from offsets, the arithmetic launch and the materialisation of
 // hc_gt_call_site records. One definition each, in gt_engine.cpp;
@@ -11,21 +11,19 @@
 
 #include <cstdint>
 #include <functional>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/hc_gt.h"
 #include "gt_kernels.hpp"
 #include "gt_plan_kernels.hpp"
+#include "stage_host.hpp"
 
 namespace hcgt_host {
 
-// Serialises every genotyper entry point; held for the whole of a call.
-std::mutex& mutex();
-// With the lock held: engine initialised, primary device current, stream and Jacobian table ready.
-int ensure_init();
-hipStream_t stream();
+// The genotyper's stage: its lock serialises every genotyper and region caller entry
+// point, and ensure_init() leaves stream and Jacobian table ready.
+stage_host::Stage& stage();
 hipError_t launch_arithmetic(hcgt::GtArgs& a);
 
 // What a region caller's input says about one region, whatever its record type.

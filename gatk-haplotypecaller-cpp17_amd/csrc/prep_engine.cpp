@@ -16,9 +16,7 @@
 
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -26,11 +24,6 @@
 #include "pool.hpp"
 #include "prep_kernels.hpp"
 #include "stage_host.hpp"
-
-namespace hcphmm {
-int primary_device();
-void prep_release();
-}
 
 using namespace hcprep;
 using namespace stage_host;
@@ -45,19 +38,8 @@ struct hc_prep_result {
 
 namespace {
 
-std::mutex g_mu;
-hipStream_t g_stream = nullptr;
 Buf g_in, g_out, g_hin{nullptr, 0, true}, g_hback{nullptr, 0, true};
-
-int ensure_init()
-{
-    const int rc = hc_phmm_init(HC_PHMM_FLAG_KEEP_MODE, -1);
-    if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
-    if (g_stream) return HC_PHMM_OK;
-    HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    return HC_PHMM_OK;
-}
+Stage g_st({&g_in, &g_out, &g_hin, &g_hback});
 
 // The HC_PHMM_EINVAL cases, before any device work. Totals the reads, and the
 // CIGAR words in front of every window (word_first, n + 1 entries).
@@ -163,20 +145,20 @@ int run(const hc_prep_window* windows, int32_t n, int64_t n_reads, const std::ve
     a.records = reinterpret_cast<hc_prep_record*>(g_out.p + o_rec);
     a.kept = reinterpret_cast<int32_t*>(g_out.p + o_kept);
 
-    HIP_TRY(g_stream, hipMemcpyAsync(g_in.p, h, in_bytes, hipMemcpyHostToDevice, g_stream));
-    HIP_TRY(g_stream, hipMemsetAsync(g_out.p + o_err, 0xFF, sizeof(unsigned long long), g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(g_in.p, h, in_bytes, hipMemcpyHostToDevice, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemsetAsync(g_out.p + o_err, 0xFF, sizeof(unsigned long long), g_st.stream));
     if (tr.on) {
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
         tr.mark("upload");
     }
-    HIP_TRY(g_stream, launch_prep(a, g_stream));
+    HIP_TRY(g_st.stream, launch_prep(a, g_st.stream));
     if (tr.on) {
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
         tr.mark("kernel");
     }
     char* hb = g_hback.p;
-    HIP_TRY(g_stream, hipMemcpyAsync(hb, g_out.p, out_bytes, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(hb, g_out.p, out_bytes, hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     tr.mark("readback");
 
     unsigned long long err = 0;
@@ -211,29 +193,17 @@ int run(const hc_prep_window* windows, int32_t n, int64_t n_reads, const std::ve
 
 extern "C" int hc_prep_reads(const hc_prep_window* windows, int32_t n_windows, hc_prep_result** out)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (n_windows < 0 || (n_windows && !windows)) return fail(HC_PHMM_EINVAL, "null windows / negative count");
-    try {
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    return call_frame(out, &g_st.stream, [&](hc_prep_result& res) -> int {
+        if (n_windows < 0 || (n_windows && !windows)) return fail(HC_PHMM_EINVAL, "null windows / negative count");
         int64_t n_reads = 0;
         std::vector<int64_t> word_first;
-        int rc = validate(windows, n_windows, n_reads, word_first);
-        if (rc) return rc;
-        std::unique_ptr<hc_prep_result> res(new hc_prep_result());
-        res->first.assign(1, 0);
-        if (n_windows) {
-            rc = ensure_init();
-            if (rc) return rc;
-            rc = run(windows, n_windows, n_reads, word_first, *res);
-            if (rc) return rc;
-        }
-        *out = res.release();
-    } catch (const std::bad_alloc&) {
-        if (g_stream) (void)hipStreamSynchronize(g_stream);
-        return fail(HC_PHMM_ENOMEM, "host allocation failed");
-    }
-    return HC_PHMM_OK;
+        if (int rc = validate(windows, n_windows, n_reads, word_first)) return rc;
+        res.first.assign(1, 0);
+        if (!n_windows) return HC_PHMM_OK;
+        if (int rc = g_st.ensure_init()) return rc;
+        return run(windows, n_windows, n_reads, word_first, res);
+    });
 }
 
 extern "C" int hc_prep_result_window(const hc_prep_result* res, int32_t window, const hc_prep_record** records,
@@ -255,14 +225,4 @@ extern "C" int hc_prep_result_free(hc_prep_result* res)
 {
     delete res;
     return HC_PHMM_OK;
-}
-
-void hcphmm::prep_release()
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_stream) return;
-    (void)hipStreamSynchronize(g_stream);
-    for (Buf* b : {&g_in, &g_out, &g_hin, &g_hback}) drop(*b);
-    (void)hipStreamDestroy(g_stream);
-    g_stream = nullptr;
 }

@@ -16,8 +16,8 @@
 //     on request the per-site read lists, the matrices and the CIGAR elements
 //
 // The workspace is the call's own: four grow-only buffers of the shared host
-// layer (stage_host.hpp), released by hc_phmm_shutdown ahead of the genotyper's.
-// Stream, lock and Jacobian table are the genotyper's, so the call serialises
+// layer (stage_host.hpp), registered with the genotyper's stage and released
+// with it. Stream, lock and Jacobian table are the genotyper's, so the call serialises
 // with hc_gt_* as those do among themselves; the frame of a region and the
 // PlanArgs / GtArgs helpers are the genotyper's too (gt_engine_internal.hpp).
 // Inside a call HIP_BAIL wraps the shared HIP error text: collect the PairHMM
@@ -39,7 +39,6 @@
 #include "sw_engine_internal.hpp"
 
 namespace hcphmm {
-void region_release();
 int submit_regions_with_mode(const hc_phmm_region* regions, int32_t n_regions, uint32_t mode, hc_phmm_job** job);
 uint32_t default_mode();
 }
@@ -50,8 +49,9 @@ using namespace stage_host;
 
 namespace {
 
-// Grow-only buffers, guarded by the genotyper's lock.
+// Grow-only buffers, guarded by the genotyper's lock and dropped with its stage.
 Buf g_dev1, g_dev2, g_hin{nullptr, 0, true}, g_hback{nullptr, 0, true};
+Stage& g_st = hcgt_host::stage().with({&g_dev1, &g_dev2, &g_hin, &g_hback});
 
 // The aligner as hc::MI355XSWAligner::align_haplotypes runs it.
 constexpr hc_sw_params kSwParams{200, -150, -260, -11};   // NEW_SW_PARAMETERS
@@ -96,7 +96,7 @@ namespace {
 
 int run(const hc_region_in* regions, int32_t n, uint32_t flags, hc_region_calls& out)
 {
-    const hipStream_t st = hcgt_host::stream();
+    const hipStream_t st = g_st.stream;
     Trace trace("HC_REGION_TRACE", "[hc_region]");
     // ---- validate and lay out
     std::vector<PlanRegion> pr(static_cast<size_t>(n));
@@ -461,30 +461,16 @@ bool region_ok(const hc_region_calls* c, int32_t region) { return c && region >=
 
 extern "C" int hc_region_call(const hc_region_in* regions, int32_t n_regions, uint32_t flags, hc_region_calls** out)
 {
-    std::lock_guard<std::mutex> lk(hcgt_host::mutex());
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
-    constexpr uint32_t known = HC_REGION_F64 | HC_REGION_DEFAULT_MODE | HC_REGION_WANT_L | HC_REGION_WANT_SITE_READS |
-                               HC_REGION_WANT_CIGARS;
-    if (flags & ~known) return fail(HC_PHMM_EINVAL, "unknown hc_region_call flags");
-    int rc = hcgt_host::ensure_init();
-    if (rc) return rc;
-    hc_region_calls* calls = nullptr;
-    try {
-        calls = new hc_region_calls();
-        calls->flags = flags;
-        if (n_regions) rc = run(regions, n_regions, flags, *calls);
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(hcgt_host::stream());
-        rc = fail(HC_PHMM_ENOMEM, "host allocation failed");
-    }
-    if (rc) {
-        delete calls;
-        return rc;
-    }
-    *out = calls;
-    return HC_PHMM_OK;
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    return call_frame(out, &g_st.stream, [&](hc_region_calls& calls) -> int {
+        if (n_regions < 0 || (n_regions && !regions)) return fail(HC_PHMM_EINVAL, "null regions / negative count");
+        constexpr uint32_t known = HC_REGION_F64 | HC_REGION_DEFAULT_MODE | HC_REGION_WANT_L | HC_REGION_WANT_SITE_READS |
+                                   HC_REGION_WANT_CIGARS;
+        if (flags & ~known) return fail(HC_PHMM_EINVAL, "unknown hc_region_call flags");
+        if (int rc = g_st.ensure_init()) return rc;
+        calls.flags = flags;
+        return n_regions ? run(regions, n_regions, flags, calls) : HC_PHMM_OK;
+    });
 }
 
 extern "C" int hc_region_calls_sites(const hc_region_calls* calls, const hc_gt_call_site** sites, int64_t* n)
@@ -546,13 +532,13 @@ extern "C" int hcx_region_finish(const double* L, int32_t n_regions, const int32
                                  const int32_t* read_len, double* L_out, uint8_t* keep, int32_t* n_kept,
                                  int64_t* order_out)
 {
-    std::lock_guard<std::mutex> lk(hcgt_host::mutex());
+    std::lock_guard<std::mutex> lk(g_st.mu);
     if (n_regions < 0 || (n_regions && (!n_reads || !n_haps || !n_kept)))
         return fail(HC_PHMM_EINVAL, "hcx_region_finish: bad argument");
-    int rc = hcgt_host::ensure_init();
+    int rc = g_st.ensure_init();
     if (rc) return rc;
     if (n_regions == 0) return HC_PHMM_OK;
-    const hipStream_t st = hcgt_host::stream();
+    const hipStream_t st = g_st.stream;
     std::vector<PlanRegion> pr(static_cast<size_t>(n_regions));
     int64_t reads = 0, L_total = 0;
     for (int32_t r = 0; r < n_regions; ++r) {
@@ -620,15 +606,4 @@ extern "C" int hcx_region_finish(const double* L, int32_t n_regions, const int32
     }
     HIP_TRY(st, hipMemcpy(n_kept, dv + o_nk, sizeof(int32_t) * size_t(n_regions), hipMemcpyDeviceToHost));
     return HC_PHMM_OK;
-}
-
-// Called by hc_phmm_shutdown, ahead of the genotyper's release (whose stream this workspace is used on).
-void hcphmm::region_release()
-{
-    std::lock_guard<std::mutex> lk(hcgt_host::mutex());
-    if (hcgt_host::stream()) (void)hipStreamSynchronize(hcgt_host::stream());
-    drop(g_dev1);
-    drop(g_dev2);
-    drop(g_hin);
-    drop(g_hback);
 }

@@ -19,9 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <mutex>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -29,11 +27,6 @@
 #include "sam_engine.hpp"
 #include "sam_kernels.hpp"
 #include "stage_host.hpp"
-
-namespace hcphmm {
-int primary_device();
-void sam_release();
-}
 
 using namespace hcsam;
 using namespace stage_host;
@@ -47,21 +40,10 @@ struct hc_sam_result {
 
 namespace {
 
-std::mutex g_mu;
-hipStream_t g_stream = nullptr;
 Buf g_text, g_chunks, g_lines, g_out, g_stage{nullptr, 0, true}, g_hback{nullptr, 0, true}, g_hsmall{nullptr, 0, true};
+Stage g_st({&g_text, &g_chunks, &g_lines, &g_out, &g_stage, &g_hback, &g_hsmall});
 
 constexpr int64_t kMaxLines = 0x7f000000;   // below kNoHeaderEnd
-
-int ensure_init()
-{
-    const int rc = hc_phmm_init(HC_PHMM_FLAG_KEEP_MODE, -1);
-    if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
-    if (g_stream) return HC_PHMM_OK;
-    HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    return HC_PHMM_OK;
-}
 
 size_t stage_bytes()
 {
@@ -103,8 +85,8 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     for (int64_t off = 0; off < len; off += int64_t(stage)) {
         const size_t n = size_t(std::min<int64_t>(int64_t(stage), len - off));
         std::memcpy(g_stage.p, text + off, n);
-        HIP_TRY(g_stream, hipMemcpyAsync(g_text.p + off, g_stage.p, n, hipMemcpyHostToDevice, g_stream));
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));   // the block is reused by the next piece
+        HIP_TRY(g_st.stream, hipMemcpyAsync(g_text.p + off, g_stage.p, n, hipMemcpyHostToDevice, g_st.stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));   // the block is reused by the next piece
     }
     a.text = reinterpret_cast<const uint8_t*>(g_text.p);
     tr.mark("upload");
@@ -119,11 +101,11 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     a.chunk_lines = reinterpret_cast<int32_t*>(g_chunks.p + o_cl);
     int64_t* chunk_first = reinterpret_cast<int64_t*>(g_chunks.p + o_cf);
     a.chunk_first = chunk_first;
-    HIP_TRY(g_stream, launch_line_count(a, g_stream));
-    HIP_TRY(g_stream, launch_scan(a.chunk_lines, a.n_chunks, chunk_first, reinterpret_cast<int64_t*>(g_chunks.p + o_cw), g_stream));
+    HIP_TRY(g_st.stream, launch_line_count(a, g_st.stream));
+    HIP_TRY(g_st.stream, launch_scan(a.chunk_lines, a.n_chunks, chunk_first, reinterpret_cast<int64_t*>(g_chunks.p + o_cw), g_st.stream));
     int64_t* small = reinterpret_cast<int64_t*>(g_hsmall.p);
-    HIP_TRY(g_stream, hipMemcpyAsync(small, chunk_first + a.n_chunks, sizeof(int64_t), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(small, chunk_first + a.n_chunks, sizeof(int64_t), hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     const int64_t n_lines = small[0];
     if (n_lines < 1 || n_lines > len) return fail(HC_PHMM_EHIP, "SAM parser: line count out of its bound");
     if (n_lines > kMaxLines) return fail(HC_PHMM_EINVAL, "more than " + std::to_string(kMaxLines) + " lines");
@@ -153,18 +135,18 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     int64_t* word_first = reinterpret_cast<int64_t*>(g_lines.p + o_wf);
     a.rec_first = rec_first;
     a.word_first = word_first;
-    HIP_TRY(g_stream, hipMemsetAsync(a.err, 0xFF, sizeof(unsigned long long), g_stream));
-    HIP_TRY(g_stream, hipMemsetAsync(a.header_end, 0x7F, sizeof(int32_t), g_stream));
-    HIP_TRY(g_stream, launch_line_write(a, g_stream));
-    HIP_TRY(g_stream, launch_parse(a, g_stream));
+    HIP_TRY(g_st.stream, hipMemsetAsync(a.err, 0xFF, sizeof(unsigned long long), g_st.stream));
+    HIP_TRY(g_st.stream, hipMemsetAsync(a.header_end, 0x7F, sizeof(int32_t), g_st.stream));
+    HIP_TRY(g_st.stream, launch_line_write(a, g_st.stream));
+    HIP_TRY(g_st.stream, launch_parse(a, g_st.stream));
     int64_t* scan_work = reinterpret_cast<int64_t*>(g_lines.p + o_lw);   // the two scans run one after the other
-    HIP_TRY(g_stream, launch_scan(a.has_record, n_lines, rec_first, scan_work, g_stream));
-    HIP_TRY(g_stream, launch_scan(a.n_words, n_lines, word_first, scan_work, g_stream));
-    HIP_TRY(g_stream, hipMemcpyAsync(small + 0, rec_first + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipMemcpyAsync(small + 1, word_first + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipMemcpyAsync(small + 2, a.err, sizeof(unsigned long long), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipMemcpyAsync(small + 3, a.header_end, sizeof(int32_t), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, launch_scan(a.has_record, n_lines, rec_first, scan_work, g_st.stream));
+    HIP_TRY(g_st.stream, launch_scan(a.n_words, n_lines, word_first, scan_work, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(small + 0, rec_first + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(small + 1, word_first + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(small + 2, a.err, sizeof(unsigned long long), hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(small + 3, a.header_end, sizeof(int32_t), hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     const int64_t n_rec = small[0], n_words = small[1];
     unsigned long long err = 0;
     std::memcpy(&err, small + 2, sizeof(err));
@@ -192,13 +174,13 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     a.records = reinterpret_cast<hc_sam_record*>(g_out.p + o_rec);
     a.line_no = reinterpret_cast<int32_t*>(g_out.p + o_ln);
     a.pool = reinterpret_cast<uint32_t*>(g_out.p + o_pool);
-    HIP_TRY(g_stream, launch_emit(a, g_stream));
+    HIP_TRY(g_st.stream, launch_emit(a, g_st.stream));
     if (tr.on) {
-        HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
         tr.mark("emit");
     }
-    HIP_TRY(g_stream, hipMemcpyAsync(g_hback.p, g_out.p, oc.off, hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(g_stream, hipStreamSynchronize(g_stream));
+    HIP_TRY(g_st.stream, hipMemcpyAsync(g_hback.p, g_out.p, oc.off, hipMemcpyDeviceToHost, g_st.stream));
+    HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));
     tr.mark("readback");
     const hc_sam_record* hr = reinterpret_cast<const hc_sam_record*>(g_hback.p + o_rec);
     const int32_t* hl = reinterpret_cast<const int32_t*>(g_hback.p + o_ln);
@@ -210,7 +192,7 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     tr.value("text_bytes", double(len));
     tr.value("lines", double(n_lines));
     tr.value("readback_bytes", double(oc.off));
-    dev.stream = g_stream;
+    dev.stream = g_st.stream;
     dev.records = a.records;
     dev.line_no = a.line_no;
     dev.n_records = int32_t(n_rec);
@@ -222,27 +204,16 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
 int hcsam::parse_resident(const uint8_t* text, int64_t text_len, hc_sam_result** out, std::unique_lock<std::mutex>& lk,
                           Resident& dev)
 {
-    std::unique_lock<std::mutex> mine(g_mu);
+    std::unique_lock<std::mutex> mine(g_st.mu);
     dev = Resident{};
-    if (!out) return fail(HC_PHMM_EINVAL, "null out");
-    *out = nullptr;
-    if (text_len < 0 || (text_len && !text)) return fail(HC_PHMM_EINVAL, "null text / negative length");
-    try {
-        std::unique_ptr<hc_sam_result> res(new hc_sam_result());
-        int rc = ensure_init();
-        if (rc) return rc;
-        dev.stream = g_stream;
-        if (text_len) {
-            rc = run(text, text_len, *res, dev);
-            if (rc) return rc;
-        }
-        *out = res.release();
-    } catch (const std::bad_alloc&) {
-        if (g_stream) (void)hipStreamSynchronize(g_stream);
-        return fail(HC_PHMM_ENOMEM, "host allocation failed");
-    }
-    lk = std::move(mine);
-    return HC_PHMM_OK;
+    const int rc = call_frame(out, &g_st.stream, [&](hc_sam_result& res) -> int {
+        if (text_len < 0 || (text_len && !text)) return fail(HC_PHMM_EINVAL, "null text / negative length");
+        if (int rc = g_st.ensure_init()) return rc;
+        dev.stream = g_st.stream;
+        return text_len ? run(text, text_len, res, dev) : HC_PHMM_OK;
+    });
+    if (!rc) lk = std::move(mine);
+    return rc;
 }
 
 extern "C" int hc_sam_parse(const uint8_t* text, int64_t text_len, hc_sam_result** out)
@@ -270,14 +241,4 @@ extern "C" int hc_sam_result_free(hc_sam_result* res)
 {
     delete res;
     return HC_PHMM_OK;
-}
-
-void hcphmm::sam_release()
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_stream) return;
-    (void)hipStreamSynchronize(g_stream);
-    for (Buf* b : {&g_text, &g_chunks, &g_lines, &g_out, &g_stage, &g_hback, &g_hsmall}) drop(*b);
-    (void)hipStreamDestroy(g_stream);
-    g_stream = nullptr;
 }

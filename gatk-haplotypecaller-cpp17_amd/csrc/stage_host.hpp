@@ -1,8 +1,12 @@
-// Host plumbing shared by the stage engines (sw_engine.cpp, gt_engine.cpp,
-// region_engine.cpp, asm_engine.cpp): the error return, 256-byte rounding, the
-// offset carver, grow-only device / pinned buffers, the phase trace and the
-// HIP_TRY macro. Host only: no .hip file includes it. The PairHMM engine's
-// pooled, multi-device buffers (engine_core.hpp) are a different design.
+// Host plumbing shared by the seven stage engines (sw_engine.cpp, gt_engine.cpp,
+// region_engine.cpp, asm_engine.cpp, prep_engine.cpp, sam_engine.cpp,
+// contig_engine.cpp) and the window caller that chains them (call_engine.cpp):
+// the error return, 256-byte rounding, the offset carver, grow-only device /
+// pinned buffers, the phase trace, the HIP_TRY macro, the Stage (an engine's
+// lock, stream, once-only setup and buffers, released by hc_phmm_shutdown
+// through release_all) and the frame of an entry point that returns a result
+// object. Host only: no .hip file includes it. The PairHMM engine's pooled,
+// multi-device buffers (engine_core.hpp) are a different design.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,12 +15,18 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
+#include <memory>
+#include <mutex>
+#include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/hc_pairhmm.h"
 
 namespace hcphmm {
 void set_last_error(const std::string& msg);
+int primary_device();
 }
 
 namespace stage_host {
@@ -114,5 +124,97 @@ inline int hip_fail(hipStream_t st, const char* expr, hipError_t e)
         hipError_t e_ = (expr);                                               \
         if (e_ != hipSuccess) return stage_host::hip_fail((st), #expr, e_);   \
     } while (0)
+
+struct Stage;
+// Every Stage of the library, in the order they were constructed (at load time), and
+// what hc_phmm_shutdown does with them (stage_host.cpp).
+std::vector<Stage*>& stages();
+void release_all();
+
+// What an engine owns on the device: its lock (held for the whole of every entry
+// point), its stream, a once-only setup with its teardown, and its buffers.
+struct Stage {
+    std::mutex mu;
+    hipStream_t stream = nullptr;   // stays null in a stage whose kernels run on another stage's stream
+    bool ready = false;             // stream and setup are complete
+
+    // setup runs once behind the stream's creation and returns 0 or an error with
+    // its message set; teardown undoes it and must be safe after a setup that failed half way.
+    Stage(std::initializer_list<Buf*> bufs, bool own_stream = true, int (*setup)(hipStream_t) = nullptr,
+          void (*teardown)() = nullptr)
+        : bufs_(bufs), own_stream_(own_stream), setup_(setup), teardown_(teardown)
+    {
+        stages().push_back(this);
+    }
+    // Further buffers that this stage's lock guards and its release drops.
+    Stage& with(std::initializer_list<Buf*> bufs)
+    {
+        bufs_.insert(bufs_.end(), bufs);
+        return *this;
+    }
+
+    // With the lock held. The PairHMM engine is initialised (an implicit init picks
+    // the device and leaves the caller's mode alone), its first device is current on
+    // the calling thread, and stream and setup are ready. A failure leaves nothing
+    // behind: the next call starts over.
+    int ensure_init(int device = -1)
+    {
+        if (int rc = hc_phmm_init(HC_PHMM_FLAG_KEEP_MODE, device)) return rc;
+        const hipError_t e = hipSetDevice(hcphmm::primary_device());
+        if (e != hipSuccess) return hip_fail(stream, "hipSetDevice(hcphmm::primary_device())", e);
+        if (ready) return HC_PHMM_OK;
+        int rc = HC_PHMM_OK;
+        if (own_stream_ && !stream) {
+            const hipError_t es = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+            if (es != hipSuccess) rc = hip_fail(stream = nullptr, "hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)", es);
+        }
+        if (!rc && setup_) rc = setup_(stream);
+        if (rc) close();
+        ready = !rc;
+        return rc;
+    }
+
+    // hc_phmm_shutdown: the next call re-creates everything on whatever device the
+    // engine is then initialised on.
+    void release()
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        close();
+    }
+
+private:
+    void close()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (teardown_) teardown_();
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+        ready = false;
+        for (Buf* b : bufs_) drop(*b);
+    }
+    std::vector<Buf*> bufs_;
+    const bool own_stream_;
+    int (*const setup_)(hipStream_t);
+    void (*const teardown_)();
+};
+
+// The frame of an entry point that hands out a result object, with the engine's
+// lock held: null check, a fresh R for body(R&) to fill, *out set only on success.
+// A host allocation that fails drains *drain (null: no stream of its own to drain).
+template <class R, class F>
+int call_frame(R** out, const hipStream_t* drain, F&& body)
+{
+    if (!out) return fail(HC_PHMM_EINVAL, "null out");
+    *out = nullptr;
+    try {
+        std::unique_ptr<R> res(new R());
+        if (int rc = body(*res)) return rc;
+        *out = res.release();
+        return HC_PHMM_OK;
+    } catch (const std::bad_alloc&) {
+        if (drain && *drain) (void)hipStreamSynchronize(*drain);
+        return fail(HC_PHMM_ENOMEM, "host allocation failed");
+    }
+}
 
 }  // namespace stage_host

@@ -30,18 +30,10 @@
 #include "stage_host.hpp"
 #include "sw_kernels.hpp"
 
-namespace hcphmm {
-int primary_device();
-void sw_release();
-}
-
 using namespace hcsw;
 using namespace stage_host;
 
 namespace {
-
-std::mutex g_mu;
-hipStream_t g_stream = nullptr;
 
 // Grow-only workspace of the synchronous entry point (hc_sw_align_flat): a
 // warm call does no hipMalloc / hipHostMalloc and one H2D + one D2H.
@@ -52,15 +44,13 @@ struct Workspace {
 
 // The aligner runs on the engine's first device slot (hc_phmm_init /
 // hc_phmm_init_devices); every entry point makes that device current on the
-// calling thread.
-int ensure_init(int device)
-{
-    const int rc = hc_phmm_init(0, device);   // device selection + gfx950 check (no-op once initialised)
-    if (rc != HC_PHMM_OK) return rc;
-    HIP_TRY(g_stream, hipSetDevice(hcphmm::primary_device()));
-    if (!g_stream) HIP_TRY(g_stream, hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    return HC_SW_OK;
-}
+// calling thread. The events are created with the workspace (ws_reserve).
+Stage g_st({&g_ws.dev, &g_ws.host}, true, nullptr, [] {
+    for (auto& e : g_ws.ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+});
 
 // The DP kernel's fast variant drops the MATRIX_MIN_CUTOFF max and reads its
 // backtrack bits as signs of differences. Both are exact when every H stays
@@ -144,7 +134,7 @@ int ws_reserve(size_t dev_bytes, size_t host_bytes)
     if (int rc = reserve(g_ws.dev, dev_bytes, "workspace device allocation")) return rc;
     if (int rc = reserve(g_ws.host, host_bytes, "workspace pinned allocation")) return rc;
     for (auto& e : g_ws.ev)
-        if (!e) HIP_TRY(g_stream, hipEventCreate(&e));
+        if (!e) HIP_TRY(g_st.stream, hipEventCreate(&e));
     return HC_SW_OK;
 }
 
@@ -263,8 +253,8 @@ int create(int64_t n, const int64_t* ref_off, const int32_t* ref_len, const uint
     std::memcpy(stage + o_order, order.data(), sizeof(int32_t) * size_t(n));
     if (ref_ext) std::memcpy(stage + o_refs, refs, size_t(ref_ext));
     if (alt_ext) std::memcpy(stage + o_alts, alts, size_t(alt_ext));
-    if (hipMemcpyAsync(b->dev, stage, in_bytes, hipMemcpyHostToDevice, g_stream) != hipSuccess ||
-        (!transient && hipStreamSynchronize(g_stream) != hipSuccess)) {
+    if (hipMemcpyAsync(b->dev, stage, in_bytes, hipMemcpyHostToDevice, g_st.stream) != hipSuccess ||
+        (!transient && hipStreamSynchronize(g_st.stream) != hipSuccess)) {
         free_batch(b);
         return fail(HC_SW_EHIP, "H2D of the batch inputs");
     }
@@ -339,7 +329,7 @@ int results(hc_sw_batch* b, int32_t* offsets, char* cigars, int32_t stride, int3
             tail_vec.resize(b->tail_bytes);
             tail = tail_vec.data();
         }
-        HIP_TRY(g_stream, hipMemcpy(tail, b->dev + b->tail_off, b->tail_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(g_st.stream, hipMemcpy(tail, b->dev + b->tail_off, b->tail_bytes, hipMemcpyDeviceToHost));
         const uint16_t* slotv = reinterpret_cast<const uint16_t*>(tail);
         const int32_t* cntv = reinterpret_cast<const int32_t*>(tail + (reinterpret_cast<char*>(b->n_elems) - (b->dev + b->tail_off)));
         const int32_t* offv = reinterpret_cast<const int32_t*>(tail + (reinterpret_cast<char*>(b->offsets) - (b->dev + b->tail_off)));
@@ -353,16 +343,16 @@ int results(hc_sw_batch* b, int32_t* offsets, char* cigars, int32_t stride, int3
             if (cnt[size_t(k)] <= kSlotElems) continue;
             if (P.empty()) {
                 P.resize(size_t(n));
-                HIP_TRY(g_stream, hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * size_t(n), hipMemcpyDeviceToHost));
+                HIP_TRY(g_st.stream, hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * size_t(n), hipMemcpyDeviceToHost));
             }
             big_at[size_t(k)] = big.size();
             big.resize(big.size() + size_t(cnt[size_t(k)]));
-            HIP_TRY(g_stream, hipMemcpy(big.data() + big_at[size_t(k)], b->elems + P[size_t(k)].el_off,
+            HIP_TRY(g_st.stream, hipMemcpy(big.data() + big_at[size_t(k)], b->elems + P[size_t(k)].el_off,
                               sizeof(uint32_t) * size_t(cnt[size_t(k)]), hipMemcpyDeviceToHost));
         }
         if (scores) {
             std::vector<SwResult> r(static_cast<size_t>(n));
-            HIP_TRY(g_stream, hipMemcpy(r.data(), b->res, sizeof(SwResult) * size_t(n), hipMemcpyDeviceToHost));
+            HIP_TRY(g_st.stream, hipMemcpy(r.data(), b->res, sizeof(SwResult) * size_t(n), hipMemcpyDeviceToHost));
             for (int64_t k = 0; k < n; ++k) scores[b->dev_ids[size_t(k)]] = r[size_t(k)].score;
         }
         for (int64_t k = 0; k < n; ++k) {
@@ -477,43 +467,43 @@ extern "C" {
 
 int hc_sw_init(int device)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    return ensure_init(device);
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    return g_st.ensure_init(device);
 }
 
 int hc_sw_batch_create(int64_t n, const int64_t* ref_off, const int32_t* ref_len, const uint8_t* refs,
                        const int64_t* alt_off, const int32_t* alt_len, const uint8_t* alts, hc_sw_params params,
                        int32_t overhang, int32_t shortcut, hc_sw_batch** out)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int rc = ensure_init(-1);
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    const int rc = g_st.ensure_init(-1);
     if (rc) return rc;
     return create(n, ref_off, ref_len, refs, alt_off, alt_len, alts, params, overhang, shortcut, out);
 }
 
 int hc_sw_batch_run(hc_sw_batch* b, void* stream)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
+    std::lock_guard<std::mutex> lk(g_st.mu);
     if (!b) return fail(HC_SW_EINVAL, "null batch");
-    const int rc = ensure_init(-1);
+    const int rc = g_st.ensure_init(-1);
     if (rc) return rc;
-    return run(b, stream ? static_cast<hipStream_t>(stream) : g_stream);
+    return run(b, stream ? static_cast<hipStream_t>(stream) : g_st.stream);
 }
 
 int hc_sw_batch_results(hc_sw_batch* b, int32_t* offsets, char* cigars, int32_t stride, int32_t* scores)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
+    std::lock_guard<std::mutex> lk(g_st.mu);
     if (!b) return fail(HC_SW_EINVAL, "null batch");
-    const int rc = ensure_init(-1);
+    const int rc = g_st.ensure_init(-1);
     if (rc) return rc;
     return results(b, offsets, cigars, stride, scores);
 }
 
 int hc_sw_batch_stats(hc_sw_batch* b, hc_sw_stats* st)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
+    std::lock_guard<std::mutex> lk(g_st.mu);
     if (!b || !st) return fail(HC_SW_EINVAL, "null batch / stats");
-    const int rc = ensure_init(-1);
+    const int rc = g_st.ensure_init(-1);
     if (rc) return rc;
     st->n_pairs = b->n;
     st->cells = b->cells;
@@ -521,9 +511,9 @@ int hc_sw_batch_stats(hc_sw_batch* b, hc_sw_stats* st)
     if (b->ran && b->nd) {
         const size_t nd = size_t(b->nd);
         std::vector<SwResult> r(nd);
-        HIP_TRY(g_stream, hipMemcpy(r.data(), b->res, sizeof(SwResult) * nd, hipMemcpyDeviceToHost));
+        HIP_TRY(g_st.stream, hipMemcpy(r.data(), b->res, sizeof(SwResult) * nd, hipMemcpyDeviceToHost));
         std::vector<SwPair> P(nd);
-        HIP_TRY(g_stream, hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * nd, hipMemcpyDeviceToHost));
+        HIP_TRY(g_st.stream, hipMemcpy(P.data(), b->pairs, sizeof(SwPair) * nd, hipMemcpyDeviceToHost));
         st->cells = 0;
         for (size_t k = 0; k < nd; ++k) {
             if (r[k].shortcut) ++st->n_shortcut;
@@ -542,7 +532,7 @@ int hc_sw_batch_stats(hc_sw_batch* b, hc_sw_stats* st)
 
 int hc_sw_batch_destroy(hc_sw_batch* b)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
+    std::lock_guard<std::mutex> lk(g_st.mu);
     free_batch(b);
     return HC_SW_OK;
 }
@@ -551,33 +541,16 @@ int hc_sw_align_flat(int64_t n, const int64_t* ref_off, const int32_t* ref_len, 
                      const int64_t* alt_off, const int32_t* alt_len, const uint8_t* alts, hc_sw_params params,
                      int32_t overhang, int32_t shortcut, int32_t* offsets, char* cigars, int32_t stride)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    int rc = ensure_init(-1);
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    int rc = g_st.ensure_init(-1);
     if (rc) return rc;
     hc_sw_batch* b = nullptr;
     rc = create(n, ref_off, ref_len, refs, alt_off, alt_len, alts, params, overhang, shortcut, &b, true);
     if (rc) return rc;
-    rc = run(b, g_stream);
+    rc = run(b, g_st.stream);
     if (!rc) rc = results(b, offsets, cigars, stride, nullptr);
     free_batch(b);
     return rc;
 }
 
 }  // extern "C"
-
-// Called by hc_phmm_shutdown: the next call re-creates the stream and workspace
-// on whatever device the engine is then initialised on.
-void hcphmm::sw_release()
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_stream) return;
-    (void)hipStreamSynchronize(g_stream);
-    drop(g_ws.dev);
-    drop(g_ws.host);
-    for (auto& e : g_ws.ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    (void)hipStreamDestroy(g_stream);
-    g_stream = nullptr;
-}

@@ -14,9 +14,10 @@ device.
 from __future__ import annotations
 
 import ctypes as C
-import re
 
+import hcbind
 import hcphmm
+from hcbind import f64p as _f64p, i32p as _i32p, i64p as _i64p, u8p as _u8p
 
 HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_asm.h")
 OK, NO_HAPLOTYPES, TOO_COMPLEX = 0, 1, 2
@@ -24,16 +25,9 @@ NOT_TRIED, SHORT_REF, TOO_MANY_KMERS, CYCLE, ACCEPTED = 0, 1, 2, 3, 4
 WANT_GRAPH = 1
 MAX_ATTEMPTS, MAX_HAPS, MAX_PATHS, MAX_REGION_READ_BASES, MAX_GRAPH_EDGES = 9, 128, 65536, 131072, 16384
 
-_u8p = C.POINTER(C.c_uint8)
-_i32p = C.POINTER(C.c_int32)
-_i64p = C.POINTER(C.c_int64)
-_f64p = C.POINTER(C.c_double)
 
-
-class AsmError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_asm error {code}: {msg}")
-        self.code = code
+class AsmError(hcbind.Error):
+    prefix = "hc_asm"
 
 
 class Read(C.Structure):
@@ -70,19 +64,16 @@ def lib():
 
 
 def declared_symbols(header: str = HEADER):
-    return sorted(set(re.findall(r"^\s*int\s+(hc_asm_\w+)\s*\(", open(header).read(), re.M)))
+    return hcbind.declared(header, "hc_asm_")
 
 
 def mirrored_symbols():
     """The entry points this module binds (for the export test)."""
-    L = lib()
-    return sorted(s for s in declared_symbols() if getattr(getattr(L, s), "argtypes", None) is not None)
+    return hcbind.mirrored(lib(), declared_symbols())
 
 
 def _check(rc: int):
-    if rc != 0:
-        msg = lib().hc_phmm_last_error()
-        raise AsmError(rc, msg.decode() if msg else "")
+    hcbind.check(rc, AsmError)
 
 
 class Prepared:

@@ -20,31 +20,26 @@ gfx950 device.
 from __future__ import annotations
 
 import ctypes as C
-import re
 
 import numpy as np
 
+import hcbind
 import hccall
 import hcgt
 import hcphmm
+import hcregion
+from hcbind import i32p as _i32p, i64p as _i64p, u32p as _u32p
 
 HEADER_SAM = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_sam.h")
 HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_contig.h")
 DEFECT_NONE, DEFECT_POS_ZERO, DEFECT_NO_CIGAR, DEFECT_CIGAR_LENGTH, DEFECT_QUAL_LENGTH, DEFECT_TOO_LONG = range(6)
-F64, DEFAULT_MODE, WANT_SITE_READS, SKIP_UNPLACED = 1, 2, 32, 256
+F64, DEFAULT_MODE, WANT_SITE_READS, SKIP_UNPLACED = 1, 2, 32, 256   # the first three are hcregion's bits
 PICK_SEEDED, PICK_FIRST = 0, 1
 PICKS = dict(seeded=PICK_SEEDED, first=PICK_FIRST)
 
-_u32p = C.POINTER(C.c_uint32)
-_i32p = C.POINTER(C.c_int32)
-_i64p = C.POINTER(C.c_int64)
 
-
-class ContigError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_contig error {code}: {msg}")
-        self.code = code
-        self.msg = msg
+class ContigError(hcbind.Error):
+    prefix = "hc_contig"
 
 
 class Record(C.Structure):
@@ -86,22 +81,16 @@ def lib():
 
 def declared_symbols(header: str | None = None):
     """The entry points of hc_sam.h and hc_contig.h (or of `header` alone)."""
-    out = set()
-    for h in ([header] if header else [HEADER_SAM, HEADER]):
-        out |= set(re.findall(r"^\s*int\s+(hc_(?:sam|contig)_\w+)\s*\(", open(h).read(), re.M))
-    return sorted(out)
+    return sorted(s for h in ([header] if header else [HEADER_SAM, HEADER]) for s in hcbind.declared(h, "hc_(?:sam|contig)_"))
 
 
 def mirrored_symbols():
     """The entry points this module binds (for the export test)."""
-    L = lib()
-    return sorted(s for s in declared_symbols() if getattr(getattr(L, s), "argtypes", None) is not None)
+    return hcbind.mirrored(lib(), declared_symbols())
 
 
 def _check(rc: int):
-    if rc != 0:
-        msg = lib().hc_phmm_last_error()
-        raise ContigError(rc, msg.decode() if msg else "")
+    hcbind.check(rc, ContigError)
 
 
 def _sam_arrays(h, accessor, with_header):
@@ -148,8 +137,8 @@ class Prepared:
         self.sam, self.ref = bytes(sam), bytes(ref)
         self.contig = contig.encode() if isinstance(contig, str) else bytes(contig)
         self.region_size, self.padding_size, self.seed, self.pick = region_size, padding_size, seed, PICKS[pick]
-        self.flags = ((DEFAULT_MODE if use_double is None else (F64 if use_double else 0))
-                      | (WANT_SITE_READS if want_site_reads else 0) | (SKIP_UNPLACED if skip_unplaced else 0))
+        self.flags = (hcregion.flags_of(want_site_reads=want_site_reads, use_double=use_double)
+                      | (SKIP_UNPLACED if skip_unplaced else 0))
 
     def run(self):
         """One hc_contig_call; returns the handle (free it with free())."""
@@ -165,21 +154,7 @@ class Prepared:
 
 def _sites(h):
     """The site records, as hccall.call_windows gives them."""
-    sites, n = C.POINTER(hcgt.CallSite)(), C.c_int64()
-    _check(lib().hc_contig_result_sites(h, C.byref(sites), C.byref(n)))
-    out = []
-    for k in range(n.value):
-        s = sites[k]
-        out.append(dict(
-            region=s.region, status=s.status, begin=s.begin, loc_end=s.loc_end, n_alleles=s.n_alleles,
-            alleles=[s.alleles[j] for j in range(s.n_alleles)] if s.alleles else [],
-            hap_allele=np.array(s.hap_allele[:s.n_haps], np.int32) if s.hap_allele else np.zeros(0, np.int32),
-            keep=np.array(s.keep[:s.n_keep], np.int32) if s.n_keep else np.zeros(0, np.int32),
-            keep_is_null=not bool(s.keep), n_keep=s.n_keep,
-            genotype_likelihoods=np.array(s.genotype_likelihoods[:s.n_genotypes], np.float64)
-            if s.genotype_likelihoods else np.zeros(0, np.float64),
-            genotype_index=s.genotype_index, a1=s.a1, a2=s.a2, genotype_quality=s.genotype_quality))
-    return out
+    return hcbind.call_sites(h, lib().hc_contig_result_sites, _check)
 
 
 def results(h):

@@ -17,21 +17,18 @@ ahead of the same arithmetic.
 from __future__ import annotations
 
 import ctypes as C
-import re
 
 import numpy as np
 
+import hcbind
 import hcphmm
+from hcbind import CallSite, f64p as _f64p, i32p as _i32p, i64p as _i64p
 
 HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_gt.h")
-_f64p = C.POINTER(C.c_double)
-_i32p = C.POINTER(C.c_int32)
 
 
-class GTError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_gt error {code}: {msg}")
-        self.code = code
+class GTError(hcbind.Error):
+    prefix = "hc_gt"
 
 
 class Site(C.Structure):
@@ -44,22 +41,11 @@ class HapAln(C.Structure):
     _fields_ = [("bases", C.c_char_p), ("length", C.c_int32), ("alignment_begin", C.c_int32), ("cigar", C.c_char_p)]
 
 
-_i64p = C.POINTER(C.c_int64)
-
-
 class Region(C.Structure):
     _fields_ = [("ref", C.c_char_p), ("ref_len", C.c_int32), ("padded_begin", C.c_int64),
                 ("origin_begin", C.c_int64), ("origin_end", C.c_int64), ("haps", C.POINTER(HapAln)),
                 ("n_haps", C.c_int32), ("read_begin", _i64p), ("read_end", _i64p), ("n_reads", C.c_int32),
                 ("L", _f64p)]
-
-
-class CallSite(C.Structure):
-    _fields_ = [("region", C.c_int32), ("status", C.c_int32), ("begin", C.c_int64), ("loc_end", C.c_int64),
-                ("n_alleles", C.c_int32), ("n_haps", C.c_int32), ("alleles", C.POINTER(C.c_char_p)),
-                ("hap_allele", _i32p), ("keep", _i32p), ("n_keep", C.c_int32), ("n_genotypes", C.c_int32),
-                ("genotype_likelihoods", _f64p), ("genotype_index", C.c_int32), ("a1", C.c_int32),
-                ("a2", C.c_int32), ("genotype_quality", C.c_int32)]
 
 
 EMITTED, HOM_REF, LOW_QUALITY_HET, TOO_MANY_ALLELES = 0, 1, 2, 3
@@ -81,7 +67,11 @@ def lib():
 
 
 def declared_symbols(header: str = HEADER):
-    return sorted(set(re.findall(r"^\s*int\s+(hc_gt_\w+)\s*\(", open(header).read(), re.M)))
+    return hcbind.declared(header, "hc_gt_")
+
+
+def _check(rc: int):
+    hcbind.check(rc, GTError)
 
 
 class Prepared:
@@ -108,10 +98,7 @@ class Prepared:
                                gi.ctypes.data_as(_i32p), gq.ctypes.data_as(_i32p))
 
     def run(self):
-        rc = lib().hc_gt_genotype_sites(self.arr, self.n)
-        if rc != 0:
-            msg = lib().hc_phmm_last_error()
-            raise GTError(rc, msg.decode() if msg else "")
+        _check(lib().hc_gt_genotype_sites(self.arr, self.n))
 
     def results(self):
         return [(gl.copy(), int(gi[0]), int(gq[0])) for gl, gi, gq in self.outs]
@@ -147,10 +134,7 @@ class PreparedRegions:
     def run(self):
         """One hc_gt_call_regions; returns the handle (free it with free())."""
         h = C.c_void_p()
-        rc = lib().hc_gt_call_regions(self.arr, self.n, C.byref(h))
-        if rc != 0:
-            msg = lib().hc_phmm_last_error()
-            raise GTError(rc, msg.decode() if msg else "")
+        _check(lib().hc_gt_call_regions(self.arr, self.n, C.byref(h)))
         return h
 
     @staticmethod
@@ -159,22 +143,7 @@ class PreparedRegions:
 
     @staticmethod
     def records(h):
-        sites, n = C.POINTER(CallSite)(), C.c_int64()
-        rc = lib().hc_gt_calls_sites(h, C.byref(sites), C.byref(n))
-        if rc != 0:
-            raise GTError(rc, "hc_gt_calls_sites")
-        out = []
-        for k in range(n.value):
-            s = sites[k]
-            out.append(dict(
-                region=s.region, status=s.status, begin=s.begin, loc_end=s.loc_end, n_alleles=s.n_alleles,
-                alleles=[s.alleles[j] for j in range(s.n_alleles)] if s.alleles else [],
-                hap_allele=np.array(s.hap_allele[:s.n_haps], np.int32) if s.hap_allele else np.zeros(0, np.int32),
-                keep=np.array(s.keep[:s.n_keep], np.int32) if s.n_keep else np.zeros(0, np.int32),
-                genotype_likelihoods=np.array(s.genotype_likelihoods[:s.n_genotypes], np.float64)
-                if s.genotype_likelihoods else np.zeros(0, np.float64),
-                genotype_index=s.genotype_index, a1=s.a1, a2=s.a2, genotype_quality=s.genotype_quality))
-        return out
+        return hcbind.call_sites(h, lib().hc_gt_calls_sites, _check, keep_counts=False)
 
 
 def call_regions(regions):

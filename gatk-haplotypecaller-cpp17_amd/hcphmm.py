@@ -22,10 +22,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
+
+import hcbind
+from hcbind import f32p as _f32p, f64p as _f64p, i32p as _i32p, i64p as _i64p, u8p as _u8p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # HC_PHMM_LIB: load another build of the library (A/B experiments only). The
@@ -36,17 +38,9 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "hc_pairhmm.h")
 
 OK, EINVAL, ENODEV, EHIP, ENOMEM = 0, -1, -2, -3, -4
 
-_u8p = C.POINTER(C.c_uint8)
-_i32p = C.POINTER(C.c_int32)
-_i64p = C.POINTER(C.c_int64)
-_f32p = C.POINTER(C.c_float)
-_f64p = C.POINTER(C.c_double)
 
-
-class PairHMMError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_phmm error {code}: {msg}")
-        self.code = code
+class PairHMMError(hcbind.Error):
+    prefix = "hc_phmm"
 
 
 class Read(C.Structure):
@@ -187,14 +181,11 @@ def check_build_id() -> dict:
 
 def declared_symbols(header: str = HEADER):
     """Every function the C header declares (for the export test)."""
-    txt = open(header).read()
-    return sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(hc_phmm_\w+)\s*\(", txt, re.M)))
+    return hcbind.declared(header, "hc_phmm_")
 
 
 def _check(rc: int):
-    if rc != OK:
-        msg = lib().hc_phmm_last_error()
-        raise PairHMMError(rc, msg.decode() if msg else "")
+    hcbind.check(rc, PairHMMError)
 
 
 def _p(a, t):

@@ -16,22 +16,17 @@ import re
 
 import numpy as np
 
+import hcbind
 import hcphmm
+from hcbind import i32p as _i32p, i64p as _i64p, u32p as _u32p
 
 HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_prep.h")
 KEPT, DROP_MAPQ, DROP_DUPLICATE, DROP_SECONDARY, DROP_MATE_CONTIG, DROP_MIN_LENGTH = 0, 1, 2, 3, 4, 5
 OPS = "MIDNSHP=X"
 
-_u32p = C.POINTER(C.c_uint32)
-_i32p = C.POINTER(C.c_int32)
-_i64p = C.POINTER(C.c_int64)
 
-
-class PrepError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_prep error {code}: {msg}")
-        self.code = code
-        self.msg = msg
+class PrepError(hcbind.Error):
+    prefix = "hc_prep"
 
 
 class Read(C.Structure):
@@ -72,19 +67,16 @@ def lib():
 
 
 def declared_symbols(header: str = HEADER):
-    return sorted(set(re.findall(r"^\s*int\s+(hc_prep_\w+)\s*\(", open(header).read(), re.M)))
+    return hcbind.declared(header, "hc_prep_")
 
 
 def mirrored_symbols():
     """The entry points this module binds (for the export test)."""
-    L = lib()
-    return sorted(s for s in declared_symbols() if getattr(getattr(L, s), "argtypes", None) is not None)
+    return hcbind.mirrored(lib(), declared_symbols())
 
 
 def _check(rc: int):
-    if rc != 0:
-        msg = lib().hc_phmm_last_error()
-        raise PrepError(rc, msg.decode() if msg else "")
+    hcbind.check(rc, PrepError)
 
 
 def pack_cigar(text: str):

@@ -15,26 +15,20 @@ device.
 from __future__ import annotations
 
 import ctypes as C
-import re
 
 import numpy as np
 
+import hcbind
 import hcgt
 import hcphmm
+from hcbind import f64p as _f64p, i32p as _i32p, i64p as _i64p, u8p as _u8p
 
 HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_region.h")
 F64, DEFAULT_MODE, WANT_L, WANT_SITE_READS, WANT_CIGARS = 1, 2, 16, 32, 64
 
-_u8p = C.POINTER(C.c_uint8)
-_i32p = C.POINTER(C.c_int32)
-_i64p = C.POINTER(C.c_int64)
-_f64p = C.POINTER(C.c_double)
 
-
-class RegionError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_region error {code}: {msg}")
-        self.code = code
+class RegionError(hcbind.Error):
+    prefix = "hc_region"
 
 
 class Hap(C.Structure):
@@ -68,19 +62,16 @@ def lib():
 
 
 def declared_symbols(header: str = HEADER):
-    return sorted(set(re.findall(r"^\s*int\s+(hc_region_\w+)\s*\(", open(header).read(), re.M)))
+    return hcbind.declared(header, "hc_region_")
 
 
 def mirrored_symbols():
     """The entry points this module binds (for the export test)."""
-    L = lib()
-    return sorted(s for s in declared_symbols() if getattr(getattr(L, s), "argtypes", None) is not None)
+    return hcbind.mirrored(lib(), declared_symbols())
 
 
 def _check(rc: int):
-    if rc != 0:
-        msg = lib().hc_phmm_last_error()
-        raise RegionError(rc, msg.decode() if msg else "")
+    hcbind.check(rc, RegionError)
 
 
 def flags_of(want_L=False, want_site_reads=False, want_cigars=False, use_double=None) -> int:
@@ -131,21 +122,7 @@ class Prepared:
 
     @staticmethod
     def sites(h):
-        sites, n = C.POINTER(hcgt.CallSite)(), C.c_int64()
-        _check(lib().hc_region_calls_sites(h, C.byref(sites), C.byref(n)))
-        out = []
-        for k in range(n.value):
-            s = sites[k]
-            out.append(dict(
-                region=s.region, status=s.status, begin=s.begin, loc_end=s.loc_end, n_alleles=s.n_alleles,
-                alleles=[s.alleles[j] for j in range(s.n_alleles)] if s.alleles else [],
-                hap_allele=np.array(s.hap_allele[:s.n_haps], np.int32) if s.hap_allele else np.zeros(0, np.int32),
-                keep=np.array(s.keep[:s.n_keep], np.int32) if s.n_keep else np.zeros(0, np.int32),
-                keep_is_null=not bool(s.keep), n_keep=s.n_keep,
-                genotype_likelihoods=np.array(s.genotype_likelihoods[:s.n_genotypes], np.float64)
-                if s.genotype_likelihoods else np.zeros(0, np.float64),
-                genotype_index=s.genotype_index, a1=s.a1, a2=s.a2, genotype_quality=s.genotype_quality))
-        return out
+        return hcbind.call_sites(h, lib().hc_region_calls_sites, _check)
 
     def keep(self, h, region: int):
         p, nr, nk = _u8p(), C.c_int32(), C.c_int32()

@@ -14,27 +14,22 @@ otherwise every call raises SWError.
 from __future__ import annotations
 
 import ctypes as C
-import re
 
 import numpy as np
 
+import hcbind
 import hcphmm
 import sw_workloads as SW
+from hcbind import i32p as _i32p, i64p as _i64p, u8p as _u8p
 
 OK, EINVAL, ENODEV, EHIP, ENOMEM, ERANGE = 0, -1, -2, -3, -4, -5
 HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_sw.h")
 MAX_LEN1, MAX_LEN2 = 1023, 1024
 SOFTCLIP, INDEL, LEADING_INDEL, IGNORE = SW.SOFTCLIP, SW.INDEL, SW.LEADING_INDEL, SW.IGNORE
 
-_u8p = C.POINTER(C.c_uint8)
-_i32p = C.POINTER(C.c_int32)
-_i64p = C.POINTER(C.c_int64)
 
-
-class SWError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"hc_sw error {code}: {msg}")
-        self.code = code
+class SWError(hcbind.Error):
+    prefix = "hc_sw"
 
 
 class Params(C.Structure):
@@ -69,14 +64,11 @@ def lib():
 
 
 def declared_symbols(header: str = HEADER):
-    txt = open(header).read()
-    return sorted(set(re.findall(r"^\s*int\s+(hc_sw_\w+)\s*\(", txt, re.M)))
+    return hcbind.declared(header, "hc_sw_")
 
 
 def _check(rc: int):
-    if rc != OK:
-        msg = lib().hc_phmm_last_error()
-        raise SWError(rc, msg.decode() if msg else "")
+    hcbind.check(rc, SWError)
 
 
 def _p(a, t):

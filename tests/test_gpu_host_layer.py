@@ -1,7 +1,9 @@
-"""The host layer the aligner, genotyper, region caller and assembler share
-(csrc/stage_host.hpp, and the region frame of gt_engine_internal.hpp): buffers
-that grow, buffers that are released and made again, and one frame with one set
-of error texts behind hc_gt_call_regions and hc_region_call.
+"""The host layer the seven stage engines share (csrc/stage_host.hpp: aligner,
+genotyper, region caller, assembler, read preparation, SAM parser and contig
+caller, with the window caller that chains them; and the region frame of
+gt_engine_internal.hpp): buffers that grow, buffers that are released and made
+again by a shutdown and the next call's init, and one frame with one set of
+error texts behind hc_gt_call_regions and hc_region_call.
 
 Every entry point goes through its Python wrapper. One fixture makes all the
 calls once, in this order, and the tests compare what it kept:
@@ -15,13 +17,16 @@ import numpy as np
 import pytest
 
 import asm_cases
+import call_cases as CC
 import gt_workloads as GW
 import region_workloads as RW
+import sam_cases as SC
 import sw_workloads as SWW
 
 pytestmark = pytest.mark.gpu
 
-ENTRIES = ("hc_sw_align_flat", "hc_gt_genotype_sites", "hc_gt_call_regions", "hc_region_call", "hc_asm_assemble")
+ENTRIES = ("hc_sw_align_flat", "hc_gt_genotype_sites", "hc_gt_call_regions", "hc_region_call", "hc_asm_assemble",
+           "hc_prep_reads", "hc_sam_parse", "hc_call_windows", "hc_contig_call")
 
 
 def _bits(x):
@@ -35,6 +40,32 @@ def _bits(x):
     if isinstance(x, (list, tuple)):
         return [_bits(v) for v in x]
     return x
+
+
+def _windows(n, seed, n_reads):
+    """n windows of call_cases.windows that have reads (its window 2 has none),
+    window k cut to its first n_reads(k) reads."""
+    wins = [w for w in CC.windows(n + 1 if n > 2 else n, seed=seed, reads_per_window=54) if w["reads"]][:n]
+    return [dict(w, reads=w["reads"][:n_reads(k)]) for k, w in enumerate(wins)]
+
+
+def _contig(n_windows, seed, n_reads):
+    """(SAM text, reference) of a contig of n_windows windows of sam_cases.REGION
+    bases: window k has n_reads(k) reads of 60 bases that cover its middle, every
+    other one with a SNP there."""
+    rng = np.random.default_rng(seed)
+    ref = CC._bases(rng, n_windows * SC.REGION)
+    hap = bytearray(ref)
+    lines = []
+    for w in range(n_windows):
+        v = w * SC.REGION + 120
+        hap[v] = CC.ACGT[(CC.ACGT.index(ref[v]) + 1) % 4]
+        for j in range(n_reads(w)):
+            at = v - 55 + j
+            src = ref if j % 2 == 0 else bytes(hap)
+            lines.append(SC.line(qname=f"w{w}r{j}", pos=at + 1, seq=src[at:at + 60].decode(), flag=(99, 147)[j % 2]))
+    order = rng.permutation(len(lines))
+    return (SC.HEADER + "".join(lines[k] + "\n" for k in order)).encode(), ref
 
 
 def _inputs():
@@ -53,13 +84,22 @@ def _inputs():
           lambda x: sum((len(r["reads"]) + len(r["ref"])) * len(r["haps"]) for r in x))
     am = ([asm_cases.random_region(909, reads=(4, 4))], [asm_cases.random_region(910 + k, reads=reads) for k in range(8)],
           lambda x: sum(len(r["ref"]) + sum(len(b) for b, _ in r["reads"]) for r in x))
-    return dict(zip(ENTRIES, (sw, gs, gr, rc, am)))
+    # one window with four reads / eight windows of 24 to 45: as windows, and as the SAM text of a contig
+    few, many = (lambda k: 4), (lambda k: 24 + 3 * k)
+    cw = (_windows(1, 920, few), _windows(8, 921, many), lambda x: sum(len(w["reads"]) for w in x))
+    pr = tuple([CC.prep_window(w) for w in x] for x in cw[:2]) + (cw[2],)
+    ct = (_contig(1, 922, few), _contig(8, 923, many), lambda x: len(x[0]))
+    sm = (ct[0][0], ct[1][0], len)
+    return dict(zip(ENTRIES, (sw, gs, gr, rc, am, pr, sm, cw, ct)))
 
 
 @pytest.fixture(scope="module")
 def runs(engine):
     import hcasm
+    import hccall
+    import hccontig
     import hcgt
+    import hcprep
     import hcregion
     import hcsw
     call = {
@@ -68,6 +108,10 @@ def runs(engine):
         "hc_gt_call_regions": hcgt.call_regions,
         "hc_region_call": lambda x: hcregion.call_regions(x, want_L=True, want_site_reads=True, want_cigars=True),
         "hc_asm_assemble": lambda x: hcasm.assemble(x, want_graph=True),
+        "hc_prep_reads": hcprep.prep_reads,
+        "hc_sam_parse": hccontig.parse_sam,
+        "hc_call_windows": lambda x: hccall.call_windows(x, want_L=True, want_site_reads=True, want_cigars=True),
+        "hc_contig_call": lambda x: hccontig.call_contig(x[0], SC.CONTIG, x[1], want_site_reads=True),
     }
     inputs = _inputs()
 
@@ -99,7 +143,9 @@ def test_results_are_not_empty(runs, entry):
     """The comparisons below compare something: every call produced records."""
     for which in ("tiny", "large"):
         r = runs[which][entry]
-        r = r["sites"] if entry == "hc_region_call" else r[1] if entry == "hc_sw_align_flat" else r
+        r = (r["sites"] if entry == "hc_region_call" else r[1] if entry == "hc_sw_align_flat"
+             else r["records"][2] if entry == "hc_sam_parse" else r["windows"] if entry in ("hc_call_windows", "hc_contig_call")
+             else r)
         assert len(r) > 0, which
 
 

@@ -217,6 +217,52 @@ def test_without_site_reads_the_lists_are_null(hcregion, regs, full):
     RC.assert_same(got, full, lists=False)
 
 
+def _frozen(x):
+    """A result as nested plain values, arrays and floats by their bytes."""
+    if isinstance(x, np.ndarray):
+        return (x.dtype.str, x.shape, x.tobytes())
+    if isinstance(x, float):
+        return np.float64(x).tobytes()
+    if isinstance(x, dict):
+        return {k: _frozen(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_frozen(v) for v in x]
+    return x
+
+
+def test_default_mode_is_the_mode_of_the_latest_init(engine, hcregion):
+    """include/hc_pairhmm.h: the mode of the caller's latest hc_phmm_init holds until
+    the next one. The aligner, the genotyper and the assembler initialise the engine
+    implicitly and must leave it alone: after init(use_double=True) and one call of
+    each, use_double=None is fp64 in hc_region_call and in hc_call_windows."""
+    import asm_cases
+    import call_cases as CC
+    import gt_workloads as GW
+    import hcasm
+    import hccall
+    import hcgt
+    import hcsw
+    import sw_workloads as SWW
+    one = RW.regions(1, seed=941, n_variants=(1, 1), n_reads=(4, 4), artefact=False)
+    assert len(one[0]["haps"]) == 2 and len(one[0]["reads"]) == 4
+    wins = CC.windows(1)
+    engine.init(0, use_double=True)
+    try:
+        hcsw.align_flat(SWW.regions(1, 2, (60, 80), seed=942))
+        hcgt.genotype_sites(*GW.sites(1, 2, reads=(4, 4), haps=(2, 2), seed=943))
+        hcasm.assemble([asm_cases.random_region(944, reads=(4, 4))])
+        reg = {m: hcregion.call_regions(one, want_L=True, use_double=m) for m in (None, True, False)}
+        win = {m: hccall.call_windows(wins, want_L=True, use_double=m) for m in (None, True, False)}
+    finally:
+        engine.init(0, use_double=False)
+    L = {m: [w["L"] for w in win[m]["windows"]] for m in win}
+    assert reg[True]["L"][0].size > 0 and L[True][0].size > 0
+    assert _frozen(reg[None]["L"]) == _frozen(reg[True]["L"]) and _frozen(reg[None]["sites"]) == _frozen(reg[True]["sites"])
+    assert _frozen(reg[True]["L"]) != _frozen(reg[False]["L"])   # or the comparison above could not fail
+    assert _frozen(L[None]) == _frozen(L[True]) and _frozen(win[None]["sites"]) == _frozen(win[True]["sites"])
+    assert _frozen(L[True]) != _frozen(L[False])
+
+
 def test_accessors_refuse_what_was_not_asked_for(hcregion, regs):
     p = hcregion.Prepared(regs[:2])
     h = p.run(hcregion.flags_of())
