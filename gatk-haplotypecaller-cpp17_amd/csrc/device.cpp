@@ -310,14 +310,7 @@ void free_part(Part* p)
     }
     if (p->slot) give_slot(p->slot);
     else if (p->dev_base) (void)hipFree(p->dev_base);
-    if (!p->slot_ev) {
-        for (auto& t : p->ev_pool)
-            for (auto& e : t) (void)hipEventDestroy(e);
-        for (auto& e : p->pack_ev)
-            if (e) (void)hipEventDestroy(e);
-        if (p->done) (void)hipEventDestroy(p->done);
-    }
-    delete p;
+    delete p;   // (~RunEvents destroys the events the part owns, not its slot's)
     std::lock_guard<std::mutex> lk(g_mu);
     --g_live_parts;
 }

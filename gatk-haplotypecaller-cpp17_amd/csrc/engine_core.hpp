@@ -1,7 +1,9 @@
 // Internal interface of the PairHMM host engine (libhcpairhmm.so), shared by
 //   device.cpp   device slots: init / shutdown, per-slot streams + workspaces
 //   planner.cpp  host planning of a part: length binning, wave packing, staging
-//   flat_plan.cpp  flat batches planned on the device (the real call path)
+//   flat_plan.cpp  flat batches planned on the device (the real call path):
+//                  plan_flat_try drives named stages; flat_records.hpp holds
+//                  its host record passes (host-only: src_view.hpp, kernels.hpp)
 //   run.cpp      the device pass of a part and the host log10 finish
 //   api.cpp      splitting calls into parts, submit / collect, the C ABI
 //
@@ -28,6 +30,7 @@
 
 #include "../../include/hc_pairhmm.h"
 #include "kernels.hpp"
+#include "src_view.hpp"
 
 namespace stage_host {
 void release_all();   // stage_host.cpp: every stage engine's stream and workspace
@@ -167,44 +170,7 @@ public:
 // ---------------------------------------------------------------------------
 // Inputs.
 
-struct ReadView {
-    int32_t len;
-    const uint8_t *bases, *q, *i, *d, *c;
-};
-struct HapView {
-    int32_t len;
-    const uint8_t* bases;
-};
-
-// Where a call's reads and haps live: flat pools (pair p = read p x hap p) or
-// struct arrays (hc_phmm_read / hc_phmm_hap).
-struct Src {
-    const int64_t* read_off = nullptr;
-    const int32_t* R = nullptr;
-    const int64_t* hap_off = nullptr;
-    const int32_t* H = nullptr;
-    const uint8_t *rs = nullptr, *q = nullptr, *ins = nullptr, *del = nullptr, *gcp = nullptr, *hap = nullptr;
-    const hc_phmm_read* reads = nullptr;
-    const hc_phmm_hap* haps = nullptr;
-
-    ReadView read(int64_t k) const
-    {
-        if (reads) {
-            const hc_phmm_read& r = reads[k];
-            return ReadView{r.length, (const uint8_t*)r.bases, (const uint8_t*)r.q, (const uint8_t*)r.i,
-                            (const uint8_t*)r.d, (const uint8_t*)r.c};
-        }
-        const int64_t o = read_off[k];
-        return ReadView{R[k], rs + o, q + o, ins + o, del + o, gcp + o};
-    }
-    HapView hapv(int64_t k) const
-    {
-        if (haps) return HapView{haps[k].length, (const uint8_t*)haps[k].bases};
-        return HapView{H[k], hap + hap_off[k]};
-    }
-    int32_t read_len(int64_t k) const { return reads ? reads[k].length : R[k]; }
-    int32_t hap_len(int64_t k) const { return haps ? haps[k].length : H[k]; }
-};
+// ReadView / HapView / Src, flat_src: src_view.hpp.
 
 // Cross-product block: reads [r0, r0+nr) x haps [h0, h0+nh) of the Src, results
 // to out[r * ostride + h] (read-major, as hc_phmm_cross / a region).
@@ -251,18 +217,127 @@ enum class PlanMode { Real, Dry };
 // one store (enqueue_results): [raw32 | raw64 | flag | run counters]. The run
 // counters (kNumCounters ints, kernels.hpp) ride along so the host sees the
 // device error word (kErrWord) with the results, at no extra transfer.
+// (part_setup.hpp res_layout lays it out.)
 struct ResLayout {
-    size_t o64, ofl, ocnt, bytes;
+    size_t o64 = 0, ofl = 0, ocnt = 0, bytes = 0;
 };
-inline ResLayout res_layout(size_t n1)
+// The block's typed pointers at `base`: the device block, the pinned host
+// image, or a host copy.
+struct ResView {
+    float* raw32;
+    double* raw64;
+    uint8_t* flag;
+    int* counters;
+};
+inline ResView res_view(char* base, const ResLayout& r)
 {
-    ResLayout r;
-    r.o64 = (sizeof(float) * n1 + 255) & ~size_t(255);
-    r.ofl = r.o64 + ((sizeof(double) * n1 + 255) & ~size_t(255));
-    r.ocnt = (r.ofl + n1 + 255) & ~size_t(255);
-    r.bytes = (r.ocnt + kNumCounters * sizeof(int) + 15) & ~size_t(15);   // whole 16-byte stores (launch_store_to_host)
-    return r;
+    return {reinterpret_cast<float*>(base), reinterpret_cast<double*>(base + r.o64),
+            reinterpret_cast<uint8_t*>(base + r.ofl), reinterpret_cast<int*>(base + r.ocnt)};
 }
+
+// ---------------------------------------------------------------------------
+// A part's events, each with its owner: a job part borrows its slot's (pack
+// pair, first run triple, done, early; Slot::ev), a batch part makes its own as
+// they are needed; a further run of either makes a triple the part owns. The
+// destructor destroys exactly the owned ones (the part's device current).
+// A batch's run triples accumulate until hc_phmm_batch_stats reads them
+// (reset_runs); they are reused after that, never shrunk.
+class RunEvents {
+public:
+    // start, end of the fp32 pass, end of the fp64 pass (not recorded when the
+    // run was solo: no fp64 launch, ev[1] ends the run).
+    struct Run {
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        bool own = false, solo = false;
+    };
+    RunEvents() = default;
+    RunEvents(const RunEvents&) = delete;
+    RunEvents& operator=(const RunEvents&) = delete;
+    ~RunEvents()
+    {
+        for (Run& r : runs_)
+            for (hipEvent_t e : r.ev)
+                if (r.own && e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : pack_)
+            if (own_pack_ && e) (void)hipEventDestroy(e);
+        if (own_done_ && done_) (void)hipEventDestroy(done_);
+    }
+    // The slot's seven (pack 0-1, the first run 2-4, done 5, early results 6).
+    void borrow(hipEvent_t const (&ev)[7])
+    {
+        pack_[0] = ev[0];
+        pack_[1] = ev[1];
+        Run r;
+        for (int k = 0; k < 3; ++k) r.ev[k] = ev[2 + k];
+        runs_.push_back(r);
+        done_ = ev[5];
+        early_ = ev[6];
+    }
+    // The pack pair, around the part's device preparation (made unless borrowed).
+    int make_pack()
+    {
+        if (pack_[0] && pack_[1]) return HC_PHMM_OK;
+        own_pack_ = true;
+        for (auto& e : pack_)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        return HC_PHMM_OK;
+    }
+    hipEvent_t pack_begin() const { return pack_[0]; }   // null: none made yet
+    hipEvent_t pack_end() const { return pack_[1]; }
+    // The next run's triple (a new one the part owns when all are in use).
+    int begin_run(Run** run)
+    {
+        if (used_ == runs_.size()) {
+            Run r;
+            r.own = true;
+            for (auto& e : r.ev)
+                if (hipEventCreate(&e) != hipSuccess) {
+                    for (hipEvent_t x : r.ev)
+                        if (x) (void)hipEventDestroy(x);
+                    return fail(HC_PHMM_EHIP, "hipEventCreate");
+                }
+            runs_.push_back(r);
+        }
+        *run = &runs_[used_++];
+        (*run)->solo = false;
+        return HC_PHMM_OK;
+    }
+    size_t n_runs() const { return used_; }   // since the last reset_runs
+    void reset_runs() { used_ = 0; }
+    // The event that ends run k.
+    hipEvent_t end_of(size_t k) const { return runs_[k].ev[runs_[k].solo ? 1 : 2]; }
+    // Device time of run k's passes once it has ended (waits for it); a solo
+    // run's fp64 time is 0.
+    hipError_t run_ms(size_t k, float* f32, float* f64) const
+    {
+        const Run& r = runs_[k];
+        *f32 = *f64 = 0;
+        hipError_t e = hipEventSynchronize(end_of(k));
+        if (e == hipSuccess) e = hipEventElapsedTime(f32, r.ev[0], r.ev[1]);
+        if (e == hipSuccess && !r.solo) e = hipEventElapsedTime(f64, r.ev[1], r.ev[2]);
+        return e;
+    }
+    // Jobs: the D2H of the results complete (made on first use unless borrowed).
+    int make_done()
+    {
+        if (done_) return HC_PHMM_OK;
+        own_done_ = true;
+        HIP_TRY(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+        return HC_PHMM_OK;
+    }
+    hipEvent_t done() const { return done_; }
+    // Jobs: the fp32 pass's raw sums and flags on the host while the fp64
+    // launch runs (run_part), so collect() finishes the unflagged pairs early.
+    hipEvent_t early() const { return early_; }   // the slot's; null: never
+    bool early_used = false;                      // the last run stored them early
+
+private:
+    hipEvent_t pack_[2] = {nullptr, nullptr};
+    hipEvent_t done_ = nullptr, early_ = nullptr;
+    bool own_pack_ = false, own_done_ = false;
+    std::vector<Run> runs_;
+    size_t used_ = 0;
+};
 
 // ---------------------------------------------------------------------------
 // A part prepared on one device: every device array lives in one allocation,
@@ -298,8 +373,7 @@ struct Part {
     float* own_raw32 = nullptr;   // outputs in the part's allocation: [raw32 | raw64 | flag]
     double* own_raw64 = nullptr;
     uint8_t* own_flag = nullptr;
-    size_t res_bytes = 0;         // bytes of that contiguous output block (ResLayout)
-    size_t res_o64 = 0, res_ofl = 0, res_ocnt = 0;
+    ResLayout res;                // that contiguous output block (res_view)
     uint4* d_rec = nullptr;       // seg slot result records (LaneArgs::rec), gathered by the fp64 launch
     int* d_slot_of = nullptr;     // pair -> seg slot (-1: one-lane / anti-diagonal pair)
     PairDesc* d_sdesc = nullptr;  // seg slot -> pair descriptor (pairs[order[slot]])
@@ -318,17 +392,7 @@ struct Part {
     Slot* slot = nullptr;         // borrowed workspace (jobs), else dev_base is owned
     char* host_res = nullptr;     // pinned results image (slot) after the D2H
     size_t upload_bytes = 0;
-    hipEvent_t pack_ev[2] = {nullptr, nullptr};
-    hipEvent_t done = nullptr;    // jobs: D2H complete
-    // Jobs: the fp32 pass's raw sums and flags on the host while the fp64
-    // launch runs (run_part), so collect() finishes the unflagged pairs early.
-    hipEvent_t early = nullptr;   // the slot's; null: never
-    bool early_used = false;      // the last run stored them early
-    std::vector<std::array<hipEvent_t, 3>> ev_pool;
-    std::vector<uint8_t> ev_solo;   // per pooled run: no fp64 launch, ev[2] not recorded (ev[1] ends the run)
-    size_t ev_used = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool slot_ev = false;         // pack_ev / ev / done are the slot's (not destroyed here)
+    RunEvents evs;                // pack, run, done and early events, the slot's or its own
     hipStream_t stream = nullptr;             // the part's stream: its slot's, else its device's
     hipStream_t side = nullptr;               // segmented waves beside one-lane waves
     hipEvent_t fork = nullptr, join = nullptr;
@@ -379,9 +443,14 @@ private:
 // (batches). part_setup.hpp holds what it shares with plan_flat_device.
 int plan_part(Device& d, const Src& src, const PartSpec& spec, Slot* slot, bool with_run, PlanMode mode,
               Part** out);
-// flat_plan.cpp: a flat part whose pairs are planned on the device; returns
-// HC_PHMM_OK with *out = nullptr when the batch needs the host planner.
-int plan_flat_device(Device& d, const Src& src, const PartSpec& spec, Slot* slot, bool with_run, Part** out);
+// flat_plan.cpp: a flat part whose pairs are planned on the device. What came
+// of it, beside the HC_PHMM_* return code (which is an error's alone): the part
+// is planned (*out), the host planner must take it, or (one attempt,
+// plan_flat_try) pass 2 refused it and it is planned again with the nibble
+// fields or with the gap planes.
+enum class FlatOutcome { Planned, HostPlanner, RetryNibbles, RetryPlanes };
+int plan_flat_device(Device& d, const Src& src, const PartSpec& spec, Slot* slot, bool with_run, Part** out,
+                     FlatOutcome* what);
 // run.cpp
 int run_part(Part* b, hipStream_t s);
 // which: every pair; the unflagged ones only (their raw f64 is 0: d unread);
@@ -394,13 +463,6 @@ void finish_part(const Part& P, const float* f, const double* d, const uint8_t* 
 // rather than a DMA copy: DMA copies run in enqueue order, so a D2H enqueued
 // behind its part's kernels held the next part's uploads until those kernels
 // finished (the parts of a call ran one after another: S2 end to end 22 ms).
-// ConvertChar codes (pairhmm_common.h:26-44: A0 C1 T2 G3 N4, other bytes 0) of n bases, two per byte,
-// base k in the low nibble of byte k / 2 when k is even (AVX2 when the CPU
-// has it; flat_plan.cpp).
-void pack_nibbles(const uint8_t* s, int n, uint8_t* d);
-// Whether a read's (i, d, c) gap qualities are the same on every row (then
-// they travel once, in its descriptor; flat_plan.cpp).
-bool constant_gaps(const uint8_t* i, const uint8_t* d, const uint8_t* c, int len);
 int enqueue_results(Part* b, hipStream_t s);
 int check_device_error(const int* counters);   // run.cpp: counters = a host copy of a part's run counters
 

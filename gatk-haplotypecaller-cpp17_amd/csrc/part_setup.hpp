@@ -23,6 +23,20 @@ struct Layout {
     }
 };
 
+// The results block of n1 = max(pairs, 1) pairs (engine_core.hpp ResLayout):
+// [raw32 | raw64 | flag | run counters], each from a 256-B boundary.
+inline ResLayout res_layout(size_t n1)
+{
+    Layout L;
+    ResLayout r;
+    L.take(sizeof(float) * n1);
+    r.o64 = L.take(sizeof(double) * n1);
+    r.ofl = L.take(n1);
+    r.ocnt = L.off;
+    r.bytes = (r.ocnt + kNumCounters * sizeof(int) + 15) & ~size_t(15);   // whole 16-byte stores (launch_store_to_host)
+    return r;
+}
+
 template <typename T>
 void grow(std::vector<T>& v, size_t n)
 {
@@ -74,14 +88,12 @@ inline RescueLayout take_rescue(Layout& L, size_t n1, size_t n_slots)
 
 inline void bind_rescue(Part& b, char* dev, const RescueLayout& o, size_t n_slots)
 {
-    b.res_bytes = o.RL.bytes;
-    b.res_o64 = o.RL.o64;
-    b.res_ofl = o.RL.ofl;
-    b.res_ocnt = o.RL.ocnt;
-    b.own_raw32 = b.d_raw32 = reinterpret_cast<float*>(dev + o.o_res);
-    b.own_raw64 = b.d_raw64 = reinterpret_cast<double*>(dev + o.o_res + o.RL.o64);
-    b.own_flag = b.d_flag = reinterpret_cast<uint8_t*>(dev + o.o_res + o.RL.ofl);
-    b.d_count = reinterpret_cast<int*>(dev + o.o_res + o.RL.ocnt);   // run counters (kNumCounters): the results block's tail
+    b.res = o.RL;
+    const ResView v = res_view(dev + o.o_res, o.RL);
+    b.own_raw32 = b.d_raw32 = v.raw32;
+    b.own_raw64 = b.d_raw64 = v.raw64;
+    b.own_flag = b.d_flag = v.flag;
+    b.d_count = v.counters;   // run counters (kNumCounters): the results block's tail
     b.d_list = reinterpret_cast<int*>(dev + o.o_list);
     b.d_sorted = reinterpret_cast<int*>(dev + o.o_sorted);
     b.d_worder = reinterpret_cast<int*>(dev + o.o_worder);
@@ -94,7 +106,7 @@ inline void bind_rescue(Part& b, char* dev, const RescueLayout& o, size_t n_slot
 
 // The part's streams and events: its slot's (Slot::ev, engine_core.hpp: pack
 // 0-1, the fp32 / fp64 passes 2-4, done 5, early results 6), else its device's
-// streams, with events of its own made as they are needed.
+// streams, with events of its own made as they are needed (RunEvents).
 inline void bind_streams(Part& b, Device& dv, Slot* slot)
 {
     if (slot) {
@@ -102,12 +114,7 @@ inline void bind_streams(Part& b, Device& dv, Slot* slot)
         b.side = slot->side;
         b.fork = slot->fork;
         b.join = slot->join;
-        b.slot_ev = true;
-        b.pack_ev[0] = slot->ev[0];
-        b.pack_ev[1] = slot->ev[1];
-        b.ev_pool.push_back({slot->ev[2], slot->ev[3], slot->ev[4]});
-        b.done = slot->ev[5];
-        b.early = slot->ev[6];
+        b.evs.borrow(slot->ev);
     } else {
         b.stream = dv.stream;
         b.side = dv.side;

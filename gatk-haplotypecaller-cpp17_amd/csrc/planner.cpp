@@ -11,6 +11,7 @@
 #include <numeric>
 
 #include "engine_core.hpp"
+#include "flat_records.hpp"   // pack_nibbles, constant_gaps
 #include "luts.hpp"
 #include "part_setup.hpp"
 #include "plan_model.hpp"
@@ -1227,7 +1228,7 @@ int enqueue_structured(Part* b, PackArgs pack, const Local& loc, const UploadLay
     } else {
         pack_sources(pack, src, U);
     }
-    HIP_TRY(hipEventRecord(b->pack_ev[0], s));
+    HIP_TRY(hipEventRecord(b->evs.pack_begin(), s));
     GridPrepArgs g{};
     g.pack = pack;
     g.blocks = reinterpret_cast<const GridBlock*>(src + im.o_gb);
@@ -1246,7 +1247,7 @@ int enqueue_structured(Part* b, PackArgs pack, const Local& loc, const UploadLay
     g.waves = b->d_lane_waves;
     g.counters = b->d_count;
     HIP_TRY(launch_prepare_grid(g, s));
-    HIP_TRY(hipEventRecord(b->pack_ev[1], s));
+    HIP_TRY(hipEventRecord(b->evs.pack_end(), s));
     return HC_PHMM_OK;
 }
 
@@ -1256,9 +1257,9 @@ int enqueue_general(Part* b, const PackArgs& pack, const Image& im, const char* 
     hipStream_t s = b->stream;
     HIP_TRY(hipMemcpyAsync(b->dev_base + im.up0, host + im.up0, im.upload - im.up0, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(b->d_count, 0, kNumCounters * sizeof(int), s));
-    HIP_TRY(hipEventRecord(b->pack_ev[0], s));
+    HIP_TRY(hipEventRecord(b->evs.pack_begin(), s));
     HIP_TRY(launch_pack_batch(pack, s));
-    HIP_TRY(hipEventRecord(b->pack_ev[1], s));
+    HIP_TRY(hipEventRecord(b->evs.pack_end(), s));
     return HC_PHMM_OK;
 }
 
@@ -1279,8 +1280,7 @@ int enqueue_upload(Part* b, const Local& loc, const UploadLayout& U, const Image
     pack.order = b->d_lane_order;
     pack.nslots = im.dev_plan ? 0 : n.n_seg_slots;   // structured plans: grid_waves writes them
     pack.sdesc = b->d_sdesc;
-    if (!b->slot_ev)
-        for (auto& e : b->pack_ev) HIP_TRY(hipEventCreate(&e));
+    if (const int rc = b->evs.make_pack()) return rc;
     const int rc = im.dev_plan ? enqueue_structured(b, pack, loc, U, im, st.host, gd, n, cfg.zero_copy_max)
                                : enqueue_general(b, pack, im, st.host);
     if (rc) return rc;

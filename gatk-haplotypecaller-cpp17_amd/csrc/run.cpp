@@ -19,14 +19,9 @@ int run_part(Part* b, hipStream_t s)
     Device& dv = *b->dev;
     b->last_stream = s;
     b->launch_waves = 0;
-    if (b->ev_used == b->ev_pool.size()) {
-        std::array<hipEvent_t, 3> t{};
-        for (auto& e : t) HIP_TRY(hipEventCreate(&e));
-        b->ev_pool.push_back(t);
-    }
-    const auto& ev = b->ev_pool[b->ev_used++];
-    for (int k = 0; k < 3; ++k) b->ev[k] = ev[k];
-    HIP_TRY(hipEventRecord(b->ev[0], s));
+    RunEvents::Run* run = nullptr;
+    if (const int rc = b->evs.begin_run(&run)) return rc;
+    HIP_TRY(hipEventRecord(run->ev[0], s));
     // No memsets: the fp32 kernels zero each pair's raw f64 slot as they emit,
     // and the rescue planner zeroes the other parity's counter for the next run.
     const int par = b->parity;
@@ -208,20 +203,21 @@ int run_part(Part* b, hipStream_t s)
         b->launch_waves += grid;
         HIP_TRY(launch_diag_f32(c.W, a, grid, s));
     }
-    HIP_TRY(hipEventRecord(b->ev[1], s));
+    HIP_TRY(hipEventRecord(run->ev[1], s));
     // Early results (a job part whose fp64 launch follows, results in place):
     // the fp32 pass's raw sums and rescue flags, final now, go to the pinned
     // image on the side stream while the fp64 launch runs, and collect()
     // finishes the unflagged pairs' log10 in that time; the fp64 sums and the
     // counters follow (enqueue_results). The 415 x 128 region's host finish
     // (~0.06 ms of log10f) overlapped its fp64 launch (~0.1 ms).
-    b->early_used = b->early && b->host_res && !solo && !all_f64 && r.rec == nullptr && b->n > 0 &&
+    b->evs.early_used = b->evs.early() && b->host_res && !solo && !all_f64 && r.rec == nullptr && b->n > 0 &&
                     b->d_raw32 == b->own_raw32 && env_i64("HC_PHMM_EARLY_FINISH", 1) != 0;
-    if (b->early_used) {
-        HIP_TRY(hipStreamWaitEvent(b->side, b->ev[1], 0));
-        HIP_TRY(launch_store_to_host(b->host_res, b->own_raw32, b->res_o64, b->side));
-        HIP_TRY(launch_store_to_host(b->host_res + b->res_ofl, b->own_flag, b->res_ocnt - b->res_ofl, b->side));
-        HIP_TRY(hipEventRecord(b->early, b->side));
+    if (b->evs.early_used) {
+        const ResView h = res_view(b->host_res, b->res);
+        HIP_TRY(hipStreamWaitEvent(b->side, run->ev[1], 0));
+        HIP_TRY(launch_store_to_host(h.raw32, b->own_raw32, b->res.o64, b->side));
+        HIP_TRY(launch_store_to_host(h.flag, b->own_flag, b->res.ocnt - b->res.ofl, b->side));
+        HIP_TRY(hipEventRecord(b->evs.early(), b->side));
     }
     if (b->n > 0 && !solo) {
         // fp64 rescue (intel_pairhmm.hpp:137-139) over the device-built list, no
@@ -250,9 +246,8 @@ int run_part(Part* b, hipStream_t s)
     // A solo run's end is ev[1]: recording ev[2] right behind it would only add
     // the marker's own stream time (~5 us measured on S1, as much as the fp64
     // launch it replaces).
-    if (!solo) HIP_TRY(hipEventRecord(b->ev[2], s));
-    if (b->ev_solo.size() < b->ev_pool.size()) b->ev_solo.resize(b->ev_pool.size());
-    b->ev_solo[b->ev_used - 1] = solo;
+    if (!solo) HIP_TRY(hipEventRecord(run->ev[2], s));
+    run->solo = solo;
     b->ran = true;
     return HC_PHMM_OK;
 }
@@ -270,15 +265,14 @@ int check_device_error(const int* counters)
 
 int enqueue_results(Part* b, hipStream_t s)
 {
-    if (b->early_used) {   // the rest: raw f64, flags again (same bytes), counters; done covers both
-        HIP_TRY(launch_store_to_host(b->host_res + b->res_o64, reinterpret_cast<const char*>(b->own_raw32) + b->res_o64,
-                                     b->res_bytes - b->res_o64, s));
-        HIP_TRY(hipStreamWaitEvent(s, b->early, 0));
+    if (b->evs.early_used) {   // the rest: raw f64, flags again (same bytes), counters; done covers both
+        HIP_TRY(launch_store_to_host(res_view(b->host_res, b->res).raw64, b->own_raw64, b->res.bytes - b->res.o64, s));
+        HIP_TRY(hipStreamWaitEvent(s, b->evs.early(), 0));
     } else {
-        HIP_TRY(launch_store_to_host(b->host_res, b->own_raw32, b->res_bytes, s));
+        HIP_TRY(launch_store_to_host(b->host_res, b->own_raw32, b->res.bytes, s));
     }
-    if (!b->done) HIP_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->done, s));
+    if (const int rc = b->evs.make_done()) return rc;
+    HIP_TRY(hipEventRecord(b->evs.done(), s));
     return HC_PHMM_OK;
 }
 

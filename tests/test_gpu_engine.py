@@ -321,3 +321,74 @@ def test_flat_rare_n_after_refusal(engine, oracle_lib):
     assert_same(engine.pairs(b), ref, "third call (compact attempt again)")
     assert L.hcx_flat_nibble_parts(-1) > 0
     L.hcx_flat_nibble_parts(0)
+
+
+def _device_plan_case(case):
+    """(batch, whether the device plans it, whether its compact attempt is refused)."""
+    if case == "one_pair":
+        return W.generate(1, (40, 120), (20, 60), 0.02, seed=71), True, False
+    if case == "one_past_a_mini_task":
+        return W.generate(513, (40, 300), (20, 150), 0.02, seed=72), True, False
+    if case in ("read_n_sampled", "read_n_unsampled"):
+        # The compact sample takes every max(1, n / 1024)-th pair: at 64 pairs it sees every read, so the part
+        # starts with the nibble fields; at 2 049 it takes the even pairs and misses pair 7, so pass 2 refuses.
+        b = W.generate(64 if case == "read_n_sampled" else 2049, (40, 300), (20, 150), 0.02, seed=73)
+        rs = b["rs"].copy()
+        rs[b["read_off"][7] + 3] = ord("N")
+        return dict(b, rs=rs), True, case == "read_n_unsampled"
+    if case == "gaps_vary":
+        b = W.generate(64, (40, 300), (20, 150), 0.02, seed=74)
+        ins = b["ins"].copy()
+        ins[b["read_off"][29] + b["R"][29] - 1] ^= 1
+        return dict(b, ins=ins), True, False
+    assert case == "long_hap"   # 4 097 bases: past 64 lanes of 64 columns, the host planner's
+    b = W.generate(8, (40, 300), (20, 150), 0.02, seed=75)
+    cut = lambda a, off, ln, p: a[off[p]:off[p] + ln[p]].tobytes()
+    pairs = [tuple(cut(b[k], b["read_off"], b["R"], p) for k in ("rs", "q", "ins", "dels", "gcp")) +
+             (cut(b["hap"], b["hap_off"], b["H"], p),) for p in range(8)]
+    long_hap = np.random.default_rng(76).choice(np.frombuffer(b"ACGT", np.uint8), 4097).tobytes()
+    pairs[3] = pairs[3][:5] + (long_hap,)
+    return W.from_pairs(pairs), False, False
+
+
+@pytest.mark.parametrize("case", ["one_pair", "one_past_a_mini_task", "read_n_sampled", "read_n_unsampled",
+                                  "gaps_vary", "long_hap"])
+def test_batch_planned_on_the_device(engine, oracle_lib, monkeypatch, case):
+    """HC_PHMM_BATCH_PLAN=device: a prepared batch through the flat planner's
+    own-memory branch (its own device allocation, tables from plain host memory,
+    the closing stream sync; a refused attempt's allocation freed before the next)
+    — one pair, one pair past a mini-task, an 'N' the compact sample sees (nibble
+    fields from the start) and one it misses (refused, then nibbles), a read whose
+    gap qualities vary in its last byte (refused, then planes), and a hap too
+    long for the device plan (the host planner takes the batch). Run twice:
+    every output field against the oracle and bit-equal to the same batch
+    planned on the host."""
+    b, on_device, refused = _device_plan_case(case)
+    n = len(b["R"])
+    ref = oracle_lib.pairs(b, nthreads=16)
+    L = engine.lib()
+
+    def run_twice():
+        L.hcx_flat_nibble_parts(0)
+        bt = engine.Batch(b)
+        try:
+            was_refused = L.hcx_flat_nibble_parts(-1) > 0
+            bt.run()
+            bt.run()
+            return bt.results(), bt.stats(), was_refused
+        finally:
+            bt.close()
+            L.hcx_flat_nibble_parts(0)
+
+    host_res, host_st, _ = run_twice()
+    monkeypatch.setenv("HC_PHMM_BATCH_PLAN", "device")
+    res, st, was_refused = run_twice()
+    assert_same(res, ref, case)
+    for k in ("loglik", "raw_f32", "raw_f64", "rescued"):
+        assert np.array_equal(bits(res[k]), bits(host_res[k])), (case, k)
+    assert st.n_runs == 2 and host_st.n_runs == 2 and st.n_pairs == n
+    assert was_refused == refused, case
+    # which planner made the batch: the two upload different images
+    assert (st.upload_bytes != host_st.upload_bytes) == on_device, case
+    if on_device:
+        assert st.n_lane_pairs == n
