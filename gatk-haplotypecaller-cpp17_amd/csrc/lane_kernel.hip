@@ -578,8 +578,12 @@ __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
     // ptab, 4 KB): no workgroup barrier between the kernel's start and a
     // wave's first loads, so the fill overlaps the wave's descriptor loads
     // (small batches are one round of waves: every wave's start-up latency is
-    // on the pass's critical path).
-    __shared__ __attribute__((aligned(32))) float ptabs[kSegWPB][kPtabLen];
+    // on the pass's critical path). The region also takes the quad table (10
+    // KB, rows of 128 bytes), which a wide wave whose qualities fit it writes
+    // over the pair table (run_seg_bc): 12.5 KB of LDS per wave with the match
+    // window, 12 waves per CU in 160 KiB.
+    __shared__ __attribute__((aligned(128))) float ptabs[kSegWPB][kPriorLdsLen];
+    static_assert(kSegWPB * (kPriorLdsLen * 4 + 5 * 64 * 8) <= 160 * 1024 / 12 * kSegWPB, "12 waves per CU");
     const int n_waves = a.n_waves_dev ? __builtin_amdgcn_readfirstlane(*a.n_waves_dev) : a.n_waves;
     const int wib = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
     const int wid = blockIdx.x * kSegWPB + wib;
@@ -598,20 +602,6 @@ __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
     fill_ptab(ptab, a.lut, __lane_id());
     __builtin_amdgcn_wave_barrier();
     seg_wave(a, wid, ptab);
-}
-
-// Wave-uniform max / min of a per-lane int (once per wave).
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return __builtin_amdgcn_readfirstlane(v);
 }
 
 // Diagnostics (Seg64Args::timeline): wave w's record.

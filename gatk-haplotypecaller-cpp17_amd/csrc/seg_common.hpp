@@ -161,10 +161,10 @@ __device__ __forceinline__ T y_next(T Ml, T Yl, T my, T yy)
 // (the pair's first column is the higher bit, as in the MSB-first window), and a
 // row reads one ds_read_b64 per two columns. The address is the row's table
 // base (32-byte aligned, once per row) with the two window bits placed at bits
-// 4:3 — a shift and a v_and_or_b32, both full rate: 2 VALU slots per two columns
-// where the carry select (prior_next) takes 6, and the reads issue on the LDS
-// port beside the other waves' VALU work. The floats multiplied are the ones
-// the select picks, so the results are the same bits.
+// 4:3 — a shift (1 slot) and a v_and_or_b32 (a three-source form, 2 slots): 3
+// VALU slots per two columns where the carry select (prior_next) takes 6, and
+// the reads issue on the LDS port beside the other waves' VALU work. The floats
+// multiplied are the ones the select picks, so the results are the same bits.
 constexpr int kPtabPairs = kQuals * 4 * 2;    // floats of the pair table
 constexpr int kPtabLen = kPtabPairs + 2 * kQuals;   // then pm[128], px[128] for the rows that keep the select
 
@@ -234,6 +234,132 @@ constexpr int kPtabMinWidth = 34;
 // LDS array itself is the limit.
 constexpr int kPtabAhead = 2;
 
+// The quad table: the same priors indexed by FOUR match bits, so one address
+// serves four columns (a shift and a v_and_or_b32 per four columns where the
+// pair table takes them per two). A quality row holds 16 patterns, 256 bytes,
+// laid out as two regions of float2 that share the address:
+//   region A [r][c] = priors of the group's first two columns (pattern bits 3, 2),
+//   region B [r][c] = priors of its last two (bits 1, 0), kQuadRegionB bytes
+//                     behind A: the second ds_read_b64 takes the address
+//                     register of the first and the DS immediate offset.
+// Rows are 128 bytes in each region, 32 of the 64 banks, so rows two apart
+// share their banks; the physical column is c = pattern ^ ((r >> 1) & 15),
+// which spreads the (skewed) patterns of lanes on such rows over all 16 bank
+// pairs (tools/lds_quad_model.py: 10.9 LDS cycles per read without, 6.2 with).
+// The XOR is applied to the row's two window words, once per row, with the
+// nibble replicated eight times.
+// 128 such rows do not fit a wave's share of the LDS (12 waves per CU in
+// 160 KiB: 13 653 bytes, 2 560 of them the match window), so the table covers
+// kQuadRows consecutive qualities from the lowest of the wave's own reads
+// (quad_scan); a wave whose reads span more keeps the pair table. The quad
+// table lies over the pair table and the pm/px arrays (one region, fill_ptab
+// first for every wave, fill_qtab over it for a quad wave).
+// HC_PTAB_NO_QUAD (EXTRA_DEV_FLAGS, A/B builds): every width keeps the pair table.
+constexpr int kQuadRows = 40;                          // Phred 2..41 spans exactly 40
+constexpr int kQuadRowBytes = 128;
+constexpr int kQuadRegionB = kQuadRows * kQuadRowBytes;   // byte offset of region B from A
+constexpr int kQuadLen = 2 * kQuadRegionB / 4;         // floats of the quad table
+// Widths whose quad form fits the register budget (168 VGPRs, no scratch).
+#ifdef HC_PTAB_NO_QUAD
+constexpr int kQuadMinWidth = 1 << 30, kQuadMaxWidth = 0;
+constexpr int kPriorLdsLen = kPtabLen;
+#else
+constexpr int kQuadMinWidth = kPtabMinWidth, kQuadMaxWidth = 64;
+constexpr int kPriorLdsLen = kQuadLen > kPtabLen ? kQuadLen : kPtabLen;
+#endif
+template <typename T, int BC>
+constexpr bool quad_width()
+{
+    return std::is_same<T, float>::value && BC >= kQuadMinWidth && BC <= kQuadMaxWidth;
+}
+
+// Wave-uniform max / min of a per-lane int (once per wave).
+__device__ __forceinline__ int wave_max(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Rows r = 4t + lane / 16 (t = 0..9), pattern p = lane & 15: one float2 store
+// per region and row. Qualities past 127 (a window that starts above 88) are
+// rows no read selects. pm and px come from the arrays behind the pair table
+// (fill_ptab), which this table overwrites: every lane reads all of its own
+// before the wave's first store.
+__device__ __forceinline__ void fill_qtab(float* tab, int lane, int qmin)
+{
+    const int p = lane & 15;
+    float pmr[kQuadRows / 4], pxr[kQuadRows / 4];
+#pragma unroll
+    for (int t = 0; t < kQuadRows / 4; ++t) {
+        const int q = min(qmin + 4 * t + (lane >> 4), kQuals - 1);
+        pmr[t] = lds_pm(tab, q);
+        pxr[t] = lds_px(tab, q);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < kQuadRows / 4; ++t) {
+        const int r = 4 * t + (lane >> 4);
+        const float pm = pmr[t], px = pxr[t];
+        const int c = p ^ ((r >> 1) & 15);
+        float2* d = reinterpret_cast<float2*>(tab + r * (kQuadRowBytes / 4) + c * 2);
+        d[0] = make_float2((p & 8) ? pm : px, (p & 4) ? pm : px);
+        d[kQuadRegionB / 8] = make_float2((p & 2) ? pm : px, (p & 1) ? pm : px);
+    }
+}
+
+// Table row and swizzle of a read row with quality q: r = q - qmin clamped
+// into the table (a prefetched row outside every read can carry any quality;
+// no result depends on what it selects), the row's base address and the
+// swizzle nibble replicated over a window word.
+__device__ __forceinline__ void quad_row(uint32_t tab_lds, uint32_t qmin, uint32_t w, uint32_t& base, uint32_t& rep)
+{
+    const uint32_t r = min(uint32_t(row_q(w)) - qmin, uint32_t(kQuadRows - 1));
+    base = tab_lds + r * kQuadRowBytes;
+    const uint32_t n6 = __umul24((r >> 1) & 15u, 0x111111u);   // six copies, full rate
+    rep = n6 | (n6 << 8);
+}
+
+// A row's table base (and, QUAD, its swizzle) from its row word.
+template <bool QUAD>
+__device__ __forceinline__ void tab_row(uint32_t tab_lds, uint32_t qmin, uint32_t w, uint32_t& base, uint32_t& rep)
+{
+    if constexpr (QUAD)
+        quad_row(tab_lds, qmin, w, base, rep);
+    else
+        base = ptab_row(tab_lds, w);
+}
+
+// Address of column group G (block columns 4G .. 4G+3) of a row: the four
+// (swizzled) window bits at bits 6:3 of the row's 128-byte-aligned base. The
+// last group of a width that is no multiple of 4 takes its low two bits from
+// the window's next columns; region A's entries do not depend on them.
+template <int G>
+__device__ __forceinline__ uint32_t quad_addr(uint32_t base, const uint2& m)
+{
+    constexpr int sh = 28 - 4 * (G & 7);
+    const uint32_t w = (G >> 3) ? m.y : m.x;
+    uint32_t bits;
+    if constexpr (sh >= 3)
+        bits = w >> (sh - 3);
+    else
+        bits = w << (3 - sh);
+    return base | (bits & 0x78u);
+}
+// Region REG (0: A, 1: B) at a group's address.
+template <int REG>
+__device__ __forceinline__ float2 quad_read(uint32_t addr)
+{
+    const float2v v = *reinterpret_cast<lds_cfloat2*>(addr + REG * kQuadRegionB);
+    return make_float2(v.x, v.y);
+}
+
 // Column J of one row, fp32 EQ path with table priors: `cell`'s EQ arithmetic
 // in the same order. pr is a ring of D pairs: on entry to an even column
 // J = 2p it holds pairs p .. p+D-1. The column takes its successor's prior,
@@ -243,9 +369,23 @@ constexpr int kPtabAhead = 2;
 // read needs registers of its own), the second lets VALU work through and
 // keeps the LDS reads where they are (hoisted to the row's start they take
 // two registers each, sunk to their use the wave waits on every one).
-template <int BC, int J, bool SUM, int D>
+// QUAD: pair P is region P & 1 at the address of group P >> 1; the address
+// (qa) is formed with the read of a group's first pair and held for the
+// second, two columns later (mrow: the swizzled window).
+template <bool QUAD, int P>
+__device__ __forceinline__ float2 tab_pair(uint32_t base, const uint2& mrow, uint32_t& qa)
+{
+    if constexpr (QUAD) {
+        if constexpr ((P & 1) == 0) qa = quad_addr<P / 2>(base, mrow);
+        return quad_read<P & 1>(qa);
+    } else {
+        return ptab_pair<P>(base, mrow);
+    }
+}
+
+template <int BC, int J, bool SUM, int D, bool QUAD>
 __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float M, float& Ml, float& Yl,
-                                         float2 (&pr)[D], uint32_t base, const uint2& mrow,
+                                         float2 (&pr)[D], uint32_t base, const uint2& mrow, uint32_t& qa,
                                          const RowConst<float>& k, float& sumM, float& sumX)
 {
     if constexpr (J < BC) {
@@ -257,7 +397,7 @@ __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float 
         if constexpr ((J & 1) == 0 && J / 2 + D < BC / 2) {
             constexpr int kNoDs = 0x2 | 0x4 | 0x10 | 0x20 | 0x40;   // VALU, SALU and VMEM may cross; DS may not
             __builtin_amdgcn_sched_barrier(0);
-            pr[(J / 2 + D) % D] = ptab_pair<J / 2 + D>(base, mrow);
+            pr[(J / 2 + D) % D] = tab_pair<QUAD, J / 2 + D>(base, mrow, qa);
             __builtin_amdgcn_sched_barrier(kNoDs);
         }
         const float Xc = X[J];
@@ -271,7 +411,7 @@ __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float 
         X[J] = Mx + Xc * k.xx;
         Ml = Mx;
         Yl = Y;
-        cell_tab<BC, J + 1, SUM, D>(Tt, X, Mn, Ml, Yl, pr, base, mrow, k, sumM, sumX);
+        cell_tab<BC, J + 1, SUM, D, QUAD>(Tt, X, Mn, Ml, Yl, pr, base, mrow, qa, k, sumM, sumX);
     }
 }
 
@@ -497,13 +637,17 @@ __device__ __forceinline__ void fill_window(uint2* __restrict__ mt, int lane, co
 // slut: the wave's prior tables in LDS. fp64: [ph2pr | pm | px | gapm]
 // (load_slut); fp32: the pair table ptab (fill_ptab), which the constant-gap
 // EQ path of the wide blocks (TAB) reads two columns at a time (cell_tab).
-template <typename T, int BC, bool CG, bool EQ>
+// QUAD (table widths of the fp32 EQ path only): slut holds the quad table of
+// the qualities qmin .. qmin + kQuadRows - 1 (fill_qtab), which cover every
+// row of the wave's reads.
+template <typename T, int BC, bool CG, bool EQ, bool QUAD = false>
 __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __restrict__ slut, const SegSteps& st,
                                         int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
-                                        uint2* __restrict__ mt)
+                                        uint2* __restrict__ mt, uint32_t qmin = 0)
 {
     constexpr int PD = seg_prefetch<T, BC>();
     constexpr bool TAB = std::is_same<T, float>::value && CG && EQ && BC >= kPtabMinWidth;
+    static_assert(!QUAD || TAB, "the quad table is a form of the table path");
     constexpr int NP = BC / 2;   // column pairs of a row (block widths are even)
     static_assert(!TAB || BC % 2 == 0, "table priors come two columns at a time");
     const int pad = ((cx.H + BC - 1) / BC) * BC - cx.H;   // zero columns left of column 1 (block 0)
@@ -513,7 +657,7 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     // hoisted above the branch between them as far as they do, where they are
     // spilled once the paths' prologues differ. A text that differs per path
     // ends that at the first instruction.
-    asm volatile("; run_seg CG=%1" : "+v"(c0) : "n"(int(CG)));
+    asm volatile("; run_seg CG=%1 QUAD=%2" : "+v"(c0) : "n"(int(CG)), "n"(int(QUAD)));
     fill_window(mt, lane, cx, c0);
     T Tt[BC], X[BC];
 #pragma unroll
@@ -534,12 +678,16 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     uint2 mrow = mt[k.rc * 64 + lane];
     // TAB: ptab's LDS address, the coming row's table base and its first
     // pair, read at the end of the step before (here: row 1's).
-    uint32_t ptab_lds = 0, base = 0;
+    // QUAD: mrow is the swizzled window (the cells of a table row do not
+    // consume it), qa the address of the group being read.
+    uint32_t ptab_lds = 0, base = 0, qa = 0;
     float2 pr0 = make_float2(0.f, 0.f);
     if constexpr (TAB) {
         ptab_lds = lds_addr(slut);
-        base = ptab_row(ptab_lds, wc);
-        pr0 = ptab_pair<0>(base, mrow);
+        uint32_t rep = 0;
+        tab_row<QUAD>(ptab_lds, qmin, wc, base, rep);
+        if constexpr (QUAD) mrow = make_uint2(mrow.x ^ rep, mrow.y ^ rep);
+        pr0 = tab_pair<QUAD, 0>(base, mrow, qa);
     }
     // A pair's last block (and any lane past it) hands zeros to the lane on its
     // right, so a group's first lane needs no select: it receives Y = 0 entering
@@ -609,11 +757,12 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
                 constexpr int D = kPtabAhead;
                 float2 pr[D];
                 pr[0] = pr0;
+                // QUAD: qa is still pr0's address (group 0), formed at the last step's end.
                 for_phases<1, (D < NP ? D : NP)>([&](auto p) {
-                    pr[decltype(p)::value] = ptab_pair<decltype(p)::value>(base, mrow);
+                    pr[decltype(p)::value] = tab_pair<QUAD, decltype(p)::value>(base, mrow, qa);
                 });
                 const float M0 = Tdiag * pr0.x;
-                cell_tab<BC, 0, SUM, D>(Tt, X, M0, Ml, Yl, pr, base, mrow, k, sumM, sumX);
+                cell_tab<BC, 0, SUM, D, QUAD>(Tt, X, M0, Ml, Yl, pr, base, mrow, qa, k, sumM, sumX);
             } else {
                 const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);   // bit 31 of mrow.x first
                 cell<T, BC, 0, BC, SUM, EQ>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
@@ -625,10 +774,17 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
             // Unconditional, as below. wn's last uses are the window's slot and
             // the table base, so the word loaded now can land in wn's register.
             const int mo = row_rc(wn) * 64 + lane;
-            base = ptab_row(ptab_lds, wn);
-            asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base));
-            mrow = mt[mo];
-            pr0 = ptab_pair<0>(base, mrow);
+            uint32_t rep = 0;
+            tab_row<QUAD>(ptab_lds, qmin, wn, base, rep);
+            if constexpr (QUAD) {
+                asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base), "v"(rep));
+                const uint2 m = mt[mo];
+                mrow = make_uint2(m.x ^ rep, m.y ^ rep);
+            } else {
+                asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base));
+                mrow = mt[mo];
+            }
+            pr0 = tab_pair<QUAD, 0>(base, mrow, qa);
             wq[P] = row_word(cx, ridx);
         } else if constexpr (CG) {
             // Unconditional (no register moves for a conditional update): a
@@ -664,6 +820,39 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     }
 }
 
+// Lowest and highest quality of the rows of the wave's reads. Lane s of a
+// pair's nb lanes takes the rows 4s .. 4s + 3, 4(s + nb) .. of its read, eight
+// 16-byte loads in flight (a load past the read's end repeats the first; the
+// rows behind a read's last are there to load, part_setup.hpp row_pad_words,
+// and are left out of the result).
+typedef uint32_t rows4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void quad_scan(const LaneCtx& cx, int s, int nb, int& qmin, int& qmax)
+{
+    int lo = kQuals - 1, hi = 0;
+    const int last = cx.R - 1;
+    constexpr int NL = 8;   // loads in flight
+    for (int i = 4 * s; i <= last; i += 4 * NL * nb) {
+        int at[NL];
+        rows4 w[NL];
+#pragma unroll
+        for (int t = 0; t < NL; ++t) {
+            at[t] = i + 4 * nb * t <= last ? i + 4 * nb * t : i;
+            w[t] = *reinterpret_cast<const rows4*>(reinterpret_cast<const char*>(cx.rbase) +
+                                                   (cx.rbyte + unsigned(at[t]) * 4u));
+        }
+#pragma unroll
+        for (int t = 0; t < NL; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = at[t] + j <= last ? row_q(w[t][j]) : lo;
+                lo = min(lo, q);
+                hi = max(hi, q);
+            }
+    }
+    qmin = wave_min(lo);
+    qmax = wave_max(hi);
+}
+
 // Two compiled paths per width: EQ (the reference's constant 'I'/'I'/'+' gap
 // qualities) and the generic per-row path (any gap qualities).
 template <typename T, int BC>
@@ -671,6 +860,20 @@ __device__ __forceinline__ void run_seg_bc(const T* __restrict__ lut, const T* _
                                            int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
                                            uint2* __restrict__ mt, bool wave_eq)
 {
+    if constexpr (quad_width<T, BC>()) {
+        // slut is the wave's prior region, writable: the quad table goes over
+        // the pair table when the wave's qualities fit its rows.
+        if (wave_eq) {
+            int qmin, qmax;
+            quad_scan(cx, s, (cx.H + BC - 1) / BC, qmin, qmax);
+            if (qmax - qmin < kQuadRows) {
+                fill_qtab(const_cast<T*>(slut), lane, qmin);
+                __builtin_amdgcn_wave_barrier();
+                run_seg<T, BC, true, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, uint32_t(qmin));
+                return;
+            }
+        }
+    }
     if (wave_eq)
         run_seg<T, BC, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt);
     else

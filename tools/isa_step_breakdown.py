@@ -25,7 +25,9 @@ fp32 EQ loops (seg_common.hpp cell_tab) has no select: per two columns one
 shift of the window word, one v_and_or_b32 that puts its two bits into the
 row's table base (priced as the other three-source forms, 2 slots) and the
 ds_read_b64 of the pair, reported as "prior table (address)" and "prior table
-(LDS read)"."""
+(LDS read)". The quad form (fill_qtab) forms that address once per four columns
+and reads twice at it, the second time with the DS immediate offset of region
+B: both reads count, and a loop with such reads is marked "quad"."""
 import collections
 import json
 import re
@@ -50,8 +52,10 @@ def operands(txt):
 
 
 def table_roles(ins):
-    """Indices of the pair table's instructions in a loop: every v_and_or_b32,
-    the shift whose result it masks, and the ds_read_b64 at its address."""
+    """Indices of the prior table's instructions in a loop: every v_and_or_b32,
+    the shift whose result it masks, and the ds_read_b64 at its address (the
+    quad form reads twice at one address, so the address stays a table address
+    until a VALU instruction overwrites its register)."""
     addr, read = set(), set()
     shift_of, addr_regs = {}, set()
     for i, (op, t) in enumerate(ins):
@@ -62,9 +66,8 @@ def table_roles(ins):
                 addr.add(shift_of.pop(a[1]))
             addr_regs.add(a[0])
             continue
-        if op == "ds_read_b64" and a[1] in addr_regs:
+        if op == "ds_read_b64" and a[1].split()[0] in addr_regs:   # "v165 offset:5120": the register
             read.add(i)
-            addr_regs.discard(a[1])
         if a and op.startswith("v_"):
             shift_of.pop(a[0], None)
             addr_regs.discard(a[0])
@@ -179,7 +182,8 @@ def main():
             by_slot[r] += slots(op, t)
             if writes_vcc(op, t):
                 carry = op == "v_add_co_u32"
-        rows.append(dict(kernel=lines[start].split(":")[0], loop=hdr, fp64=fp64, bc=bc, eq=eq, row_sums=sums, steps_per_iteration=steps,
+        quad = any(op == "ds_read_b64" and "offset:" in t for i, (op, t) in enumerate(ins) if i in tab_read)
+        rows.append(dict(kernel=lines[start].split(":")[0], loop=hdr, fp64=fp64, bc=bc, eq=eq, quad=quad, row_sums=sums, steps_per_iteration=steps,
                          s_nop_per_step=round(c["s_nop"] / steps, 2),
                          select_ops_per_step={k: round(c[k] / steps, 2) for k in
                                               ("v_add_co_u32", "v_cndmask_b32", "v_bfe_i32", "v_bitop3_b32")},
@@ -192,7 +196,7 @@ def main():
                          total_instr_per_step=round(len(ins) / steps, 2),
                          valu_instr_per_step=round(sum(n for op, n in c.items() if op.startswith("v_")) / steps, 2),
                          valu_slots_per_step=round(sum(by_slot.values()) / steps, 2)))
-    rows.sort(key=lambda r: (r["fp64"], not r["eq"], r["row_sums"], r["bc"]))
+    rows.sort(key=lambda r: (r["fp64"], not r["eq"], r["row_sums"], r["bc"], r["quad"]))
     for r in rows:
         print(json.dumps(r))
     if out_json:
