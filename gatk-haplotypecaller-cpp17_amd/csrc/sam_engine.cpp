@@ -196,6 +196,8 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     dev.records = a.records;
     dev.line_no = a.line_no;
     dev.n_records = int32_t(n_rec);
+    dev.text = a.text;
+    dev.text_len = len;
     return HC_PHMM_OK;
 }
 

@@ -1,6 +1,6 @@
-// Host plumbing shared by the seven stage engines (sw_engine.cpp, gt_engine.cpp,
+// Host plumbing shared by the eight stage engines (sw_engine.cpp, gt_engine.cpp,
 // region_engine.cpp, asm_engine.cpp, prep_engine.cpp, sam_engine.cpp,
-// contig_engine.cpp) and the window caller that chains them (call_engine.cpp):
+// contig_engine.cpp, genome_engine.cpp) and the window caller that chains them (call_engine.cpp):
 // the error return, 256-byte rounding, the offset carver, grow-only device /
 // pinned buffers, the phase trace, the HIP_TRY macro, the Stage (an engine's
 // lock, stream, once-only setup and buffers, released by hc_phmm_shutdown
