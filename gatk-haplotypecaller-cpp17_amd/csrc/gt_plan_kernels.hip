@@ -312,10 +312,12 @@ __global__ __launch_bounds__(64) void gt_plan_site_kernel(PlanArgs a, int n_site
             if (s_cov[h]) v = max(v, star_allele);
             a.amap[map_off + h] = v;
         }
-        // Interval::overlaps with the allele window widened by 2 on both sides, in
-        // unsigned arithmetic as the reference (begin - 2 wraps for begin < 2).
+        // Interval::overlaps with the allele window widened by 2 on both sides and
+        // cut at the contig's first base. For begin < 2 the reference's begin - 2
+        // wraps and its Interval constructor throws (interval.hpp:26-31,82-83), so
+        // there the window is ours to define: expand_within_contig as it is named.
         const uint64_t begin = uint64_t(R.padded_begin + p);
-        const uint64_t w_lo = begin - 2u, w_hi = begin + uint64_t(c.R) + 2u;
+        const uint64_t w_lo = begin < 2u ? 0u : begin - 2u, w_hi = begin + uint64_t(c.R) + 2u;
         for (int r0 = 0; r0 < R.n_reads; r0 += 64) {
             const int i = r0 + lane;
             bool on = false;

@@ -115,7 +115,8 @@ typedef struct hc_gt_call_site {
     int32_t n_haps;           /* length of hap_allele (0 when NULL) */
     const char* const* alleles; /* n_alleles strings: the reference allele, then the alts sorted bytewise */
     const int32_t* hap_allele;
-    const int32_t* keep;      /* ascending read indices overlapping [begin - 2, loc_end + 2) */
+    const int32_t* keep;      /* ascending read indices overlapping [max(begin, 2) - 2, loc_end + 2): the
+                               * window is cut at the contig's first base, where the reference throws */
     int32_t n_keep;
     int32_t n_genotypes;      /* n_alleles * (n_alleles + 1) / 2 */
     const double* genotype_likelihoods;

@@ -12,10 +12,11 @@
  *
  * Pinning: approximate_log10_sum_log10 and its Jacobian table are checked
  * against the reference's own math_utils.hpp compiled in place
- * (oracle/_ref/libref_math.so, tests/golden/gt_golden.npz). genotyper.hpp
- * itself includes sam.hpp (Boost) and cannot be compiled here, so the loops
- * above are a restatement (their fixtures are regression pins, not reference
- * outputs).
+ * (oracle/_ref/libref_math.so, tests/golden/gt_golden.npz). The loops above are
+ * checked against genotyper.hpp itself, compiled in place by
+ * oracle/ref_chain_driver.cpp (oracle/_ref/libref_chain.so): the site fixtures
+ * of gt_golden.npz and the sites of tests/golden/chain_golden.npz are the
+ * reference's outputs, and tests/test_ref_pins.py compares every one bit for bit.
  */
 #ifndef HC_GT_ORACLE_H
 #define HC_GT_ORACLE_H

@@ -226,3 +226,239 @@ class MathReference:
 
     def approx(self, a: float, b: float) -> float:
         return self.lib.ref_approx_log10_sum_log10(a, b)
+
+
+# --------------------------------------------------------------------------
+# The reference's region chain compiled in place (oracle/_ref/libref_chain.so,
+# oracle/ref_chain_driver.cpp): SAM parse, read filters and clipper, the
+# aligner's front, IntelPairHMM::compute_likelihoods and the Genetyper.
+REF_CHAIN_SO = os.path.join(HERE, "_ref", "libref_chain.so")
+CHAIN_CONTIG = "c"   # the RNAME every read handed to the driver carries
+
+
+class ReferenceThrew(Exception):
+    """The reference threw a std::exception on this input."""
+
+
+class _Blob:
+    """Reader of the driver's blobs: little-endian int64 / double / length-prefixed bytes."""
+
+    def __init__(self, raw: bytes):
+        self.raw, self.at = raw, 0
+
+    def i64(self) -> int:
+        v = int.from_bytes(self.raw[self.at:self.at + 8], "little", signed=True)
+        self.at += 8
+        return v
+
+    def u64(self) -> int:
+        v = int.from_bytes(self.raw[self.at:self.at + 8], "little", signed=False)
+        self.at += 8
+        return v
+
+    def f64s(self, n: int) -> np.ndarray:
+        v = np.frombuffer(self.raw, np.float64, n, self.at).copy()
+        self.at += 8 * n
+        return v
+
+    def i64s(self, n: int) -> np.ndarray:
+        v = np.frombuffer(self.raw, np.int64, n, self.at).copy()
+        self.at += 8 * n
+        return v
+
+    def bytes_(self) -> bytes:
+        n = self.i64()
+        v = self.raw[self.at:self.at + n]
+        self.at += n
+        return v
+
+    def end(self):
+        assert self.at == len(self.raw), (self.at, len(self.raw))
+
+
+def sam_line(k, flag, pos, mapq, cigar, mate_same, seq, qual) -> str:
+    """One read as the driver takes it: QNAME is the read's index, RNAME the driver's contig."""
+    return "\t".join(str(x) for x in (k, flag, CHAIN_CONTIG, pos, mapq, cigar, "=" if mate_same else "chrOther", 0, 0,
+                                      seq, qual))
+
+
+def interval_sam(read_begin, read_end) -> str:
+    """Reads of which only get_interval() matters (the genotyper's)."""
+    return "\n".join(sam_line(k, 0, int(b) + 1, 60, f"{int(e) - int(b)}M", 1, "*", "*")
+                     for k, (b, e) in enumerate(zip(read_begin, read_end)))
+
+
+def haps_text(haps) -> str:
+    """[{bases, begin, cigar}] (or bare bases, not aligned yet) as the driver takes them."""
+    out = []
+    for h in haps:
+        if isinstance(h, (bytes, str)):
+            h = dict(bases=h, begin=0, cigar="-")
+        b = h["bases"].decode("latin-1") if isinstance(h["bases"], bytes) else h["bases"]
+        out.append(f"{b} {h['begin']} {h['cigar']}")
+    return "\n".join(out)
+
+
+class ChainReference:
+    """The hcr_* entries. Each returns plain Python / numpy data and raises
+    ReferenceThrew where the reference threw."""
+
+    THREW, SMALL, BAD_INPUT = -1, -2, -3
+
+    def __init__(self, path: str = REF_CHAIN_SO):
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self.lib = L = C.CDLL(path)
+        tail = [_u8p, C.c_long]
+        L.hcr_parse.argtypes = [C.c_char_p, C.c_long] + tail
+        L.hcr_prepare.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64] + tail
+        L.hcr_align.argtypes = [C.c_char_p, C.c_long, C.c_char_p, C.c_long] + [C.c_int] * 4 + tail
+        L.hcr_likelihoods.argtypes = [C.c_char_p, C.c_char_p] + tail
+        L.hcr_normalize.argtypes = [C.c_char_p, C.c_long, _f64p] + tail
+        L.hcr_normalize.restype = C.c_long
+        L.hcr_gt_site.argtypes = [_f64p, C.c_long, C.c_long, _i32p, C.c_long, _i32p, C.c_long] + tail
+        L.hcr_gt_site.restype = C.c_long
+        L.hcr_genotype.argtypes = [C.c_char_p, C.c_char_p, _f64p, C.c_char_p, C.c_long] + [C.c_uint64] * 4 + tail
+        L.hcr_chain.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_long] + [C.c_uint64] * 4 + tail
+        for f in (L.hcr_parse, L.hcr_prepare, L.hcr_align, L.hcr_likelihoods, L.hcr_genotype, L.hcr_chain):
+            f.restype = C.c_long
+
+    def _call(self, fn, *args) -> _Blob:
+        cap = 1 << 16
+        while True:
+            buf = np.zeros(cap, np.uint8)
+            n = fn(*args, _ptr(buf, _u8p), cap)
+            if n == self.SMALL:
+                cap *= 8
+                continue
+            if n == self.THREW:
+                raise ReferenceThrew()
+            if n < 0:
+                raise ValueError("input the reference driver refuses")
+            return _Blob(buf[:n].tobytes())
+
+    @staticmethod
+    def _enc(s) -> bytes:
+        return s if isinstance(s, bytes) else s.encode("latin-1")
+
+    def parse(self, line):
+        """dict(fail, FLAG, POS, MAPQ, elements [(length, op)], RNEXT, PNEXT, TLEN, SEQ, QUAL)."""
+        raw = self._enc(line)
+        b = self._call(self.lib.hcr_parse, raw, len(raw))
+        out = dict(fail=b.i64(), FLAG=b.i64(), POS=b.i64(), MAPQ=b.i64())
+        out["elements"] = [(b.u64(), chr(b.i64())) for _ in range(b.i64())]
+        out.update(RNEXT=b.bytes_().decode("latin-1"), PNEXT=b.i64(), TLEN=b.i64(), SEQ=b.bytes_().decode("latin-1"),
+                   QUAL=b.bytes_().decode("latin-1"))
+        b.end()
+        return out
+
+    def prepare(self, sam: str, begin: int, end: int):
+        """Per input read dict(reason, left (bool), and for a survivor POS, CIGAR, SEQ, QUAL)."""
+        b = self._call(self.lib.hcr_prepare, self._enc(sam), begin, end)
+        out = []
+        for _ in range(b.i64()):
+            r = dict(reason=b.i64(), left=not b.i64())
+            if not r["left"]:
+                r.update(POS=b.i64(), CIGAR=b.bytes_().decode(), SEQ=b.bytes_().decode("latin-1"),
+                         QUAL=b.bytes_().decode("latin-1"))
+            out.append(r)
+        b.end()
+        return out
+
+    def align(self, ref, alt, params=(200, -150, -260, -11)):
+        ref, alt = self._enc(ref), self._enc(alt)
+        b = self._call(self.lib.hcr_align, ref, len(ref), alt, len(alt), *params)
+        out = (b.u64(), b.bytes_().decode())
+        b.end()
+        return out
+
+    def likelihoods(self, sam: str, haps):
+        """dict(raw (reads x haps, before normalisation), kept (indices), L (kept x haps))."""
+        b = self._call(self.lib.hcr_likelihoods, self._enc(sam), self._enc(haps_text(haps)))
+        nr, nh = b.i64(), b.i64()
+        raw = b.f64s(nr * nh).reshape(nr, nh)
+        nk = b.i64()
+        kept = b.i64s(nk)
+        L = b.f64s(nk * nh).reshape(nk, nh)
+        b.end()
+        return dict(raw=raw, kept=kept, L=L)
+
+    def normalize(self, L, read_len):
+        """normalize_likelihoods_and_filter_poorly_modeled_reads on a matrix handed in: (kept indices, L left)."""
+        L = np.ascontiguousarray(L, np.float64)
+        sam = "\n".join(sam_line(k, 0, 1, 60, f"{int(n)}M", 1, "A" * int(n), "I" * int(n)) for k, n in enumerate(read_len))
+        b = self._call(self.lib.hcr_normalize, self._enc(sam), L.shape[1], _ptr(L, _f64p))
+        nk = b.i64()
+        kept = b.i64s(nk)
+        out = b.f64s(nk * L.shape[1]).reshape(nk, L.shape[1])
+        b.end()
+        return kept, out
+
+    def site(self, L, keep, hap_allele, n_alleles):
+        """One site's arithmetic, as GTOracle.site: (genotype likelihoods, index, quality)."""
+        L = np.ascontiguousarray(L, np.float64)
+        keep = np.ascontiguousarray(keep, np.int32)
+        amap = np.ascontiguousarray(hap_allele, np.int32)
+        b = self._call(self.lib.hcr_gt_site, _ptr(L, _f64p), L.shape[0], L.shape[1], _ptr(keep, _i32p), len(keep),
+                       _ptr(amap, _i32p), n_alleles)
+        out = (b.f64s(n_alleles * (n_alleles + 1) // 2), b.i64(), b.i64())
+        b.end()
+        return out
+
+    @staticmethod
+    def _variants(b: _Blob):
+        out = []
+        for _ in range(b.i64()):
+            v = dict(begin=b.u64(), end=b.u64())
+            v["alleles"] = [b.bytes_() for _ in range(b.i64())]
+            v.update(a1=b.i64(), a2=b.i64(), gq=b.i64(), text=b.bytes_().decode("latin-1"))
+            out.append(v)
+        return out
+
+    def genotype(self, region):
+        """A region in hcgt.call_regions' layout. dict(threw, variants, sites):
+        `threw` / `variants` are assign_genotype_likelihoods' own outcome; `sites`
+        has, per events_begins entry inside the origin, dict(begin, threw) and,
+        where the site did not throw, loc_begin, loc_end, alleles and (for at most
+        7 alleles) hap_allele, keep, genotype_likelihoods, genotype_index,
+        genotype_quality."""
+        L = np.ascontiguousarray(region["L"], np.float64)
+        ref = self._enc(region["ref"])
+        pb = int(region["padded_begin"])
+        b = self._call(self.lib.hcr_genotype, self._enc(interval_sam(region["read_begin"], region["read_end"])),
+                       self._enc(haps_text(region["haps"])), _ptr(L if L.size else np.zeros(1), _f64p), ref, len(ref),
+                       pb, pb + len(ref), int(region["origin_begin"]), int(region["origin_end"]))
+        out = dict(threw=bool(b.i64()), variants=[], sites=[])
+        if not out["threw"]:
+            out["variants"] = self._variants(b)
+        nh = len(region["haps"])
+        for _ in range(b.i64()):
+            s = dict(begin=b.u64(), threw=bool(b.i64()))
+            if not s["threw"]:
+                s.update(loc_begin=b.u64(), loc_end=b.u64())
+                s["alleles"] = [b.bytes_() for _ in range(b.i64())]
+                A = len(s["alleles"])
+                if A <= 7:
+                    s["hap_allele"] = b.i64s(nh).astype(np.int32)
+                    s["keep"] = b.i64s(b.i64()).astype(np.int32)
+                    s["genotype_likelihoods"] = b.f64s(A * (A + 1) // 2)
+                    s.update(genotype_index=b.i64(), genotype_quality=b.i64())
+            out["sites"].append(s)
+        b.end()
+        return out
+
+    def chain(self, sam: str, haps, ref, padded_begin, origin_begin, origin_end):
+        """dict(outcome (0 called, 1 no reads left, 2 at most one haplotype), n_reads, variants)."""
+        ref = self._enc(ref)
+        b = self._call(self.lib.hcr_chain, self._enc(sam), self._enc(haps_text(haps)), ref, len(ref), padded_begin,
+                       padded_begin + len(ref), origin_begin, origin_end)
+        out = dict(outcome=b.i64(), n_reads=0, variants=[])
+        if out["outcome"] == 0:
+            out["n_reads"] = b.i64()
+            out["variants"] = self._variants(b)
+        b.end()
+        return out
+
+
+def chain_reference_available() -> bool:
+    return os.path.exists(REF_CHAIN_SO)

@@ -9,8 +9,11 @@
 //
 // The flags in the Makefile are the reference's own (-O3 -mavx -mavx2,
 // CMakeLists.txt:5) plus -fopenmp for the multi-core baseline. The driver
-// restates only the 10-line rescue/log10 loop of intel_pairhmm.hpp:131-146,
-// because intel_pairhmm.hpp itself pulls Boost headers that are absent here.
+// restates the 10-line rescue/log10 loop of intel_pairhmm.hpp:131-146 over
+// independent pairs (ref_pairs: the layout the fixtures and the timing want).
+// The header's own loop, with getData and the normalisation behind it, is
+// compiled in place by ref_chain_driver.cpp, and tests/test_ref_pins.py holds
+// the two to the same bits.
 #include <cmath>
 #include <cstdint>
 #include <cstring>

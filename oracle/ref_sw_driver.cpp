@@ -7,9 +7,12 @@
 // and to time the reference aligner beside the GPU in bench.py.
 //
 // The flags are the reference's own (-O3 -mavx -mavx2, CMakeLists.txt:5).
-// IntelSWAligner::align (intel_smithwaterman.hpp:29-44) needs cigar.hpp, which
-// pulls Boost (absent here), so its 10-line all-match shortcut is restated in
-// ref_sw_align_batch and runSWOnePairBT_avx2 is called directly.
+// ref_sw_align_batch calls runSWOnePairBT_avx2 directly over a flat batch, with
+// every overhang strategy, and restates the 10-line all-match shortcut of
+// IntelSWAligner::align (intel_smithwaterman.hpp:29-58) for it.
+// IntelSWAligner::align itself, shortcut and Cigar(char*) included, is compiled
+// in place by ref_chain_driver.cpp; tests/test_ref_pins.py pins the restated
+// shortcut to it.
 #include <algorithm>
 #include <climits>
 #include <cstdint>

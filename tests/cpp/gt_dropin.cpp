@@ -192,7 +192,7 @@ static void host_region(const RegionIn& r, HostSums& sums)
             }
             sums.map_sum += best;
         }
-        const std::size_t lo = begin - 2, hi = loc_end + 2;
+        const std::size_t lo = begin < 2 ? 0 : begin - 2, hi = loc_end + 2;   // cut at the contig's first base (hc_gt.h)
         for (const auto& rec : r.reads)
             if (rec.iv.begin < hi && lo < rec.iv.end) sums.kept += 1;
     }

@@ -15,9 +15,11 @@
 // likelihood matrices, per-site genotype likelihoods, genotype and quality.
 //
 // The event bookkeeping between the kernels (CIGAR -> events -> alleles ->
-// haplotype/read maps) is the harness's own, shared by both chains: the
-// reference's genotyper.hpp needs Boost (sam.hpp) and cannot be built here.
-// VCF parity with the reference binary stays unpinned (Boost and chrM absent).
+// haplotype/read maps) is the harness's own, shared by both chains; the
+// reference's own bookkeeping (genotyper.hpp compiled in place) is what
+// tests/test_ref_pins.py and tests/test_gpu_ref_pins.py compare against.
+// VCF parity with the reference binary stays unpinned: the assembler needs
+// Boost.Graph, which is absent, and so is chrM.
 //
 // usage: region_pipeline <n_regions> <seed> <out.json>
 #include <algorithm>

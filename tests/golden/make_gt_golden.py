@@ -8,10 +8,12 @@ Writes tests/golden/gt_golden.npz:
                                    in place (oracle/_ref/libref_math.so): random
                                    pairs, every table step near the 8.0 tolerance,
                                    ties, rounding half-steps, -DBL_MAX and -inf
-  site fixtures                    gt_workloads.sites() inputs and the ORACLE's
-                                   genotype likelihoods / index / quality (a
-                                   regression pin: genotyper.hpp includes Boost via
-                                   sam.hpp and cannot be compiled here)
+  site fixtures                    gt_workloads.sites() inputs and the REFERENCE's
+                                   genotype likelihoods / index / quality, from
+                                   genotyper.hpp's own marginal_likelihoods,
+                                   calculate_genotype_likelihoods and
+                                   get_genotype_quality_and_max_genotype_index
+                                   compiled in place (oracle/_ref/libref_chain.so)
 """
 from __future__ import annotations
 
@@ -51,7 +53,7 @@ def main():
     rng = np.random.default_rng(60)
     a, b = approx_inputs(rng)
     out = dict(approx_a=a, approx_b=b, approx_out=np.array([ref.approx(x, y) for x, y in zip(a, b)]))
-    orc = oracle.GTOracle()
+    orc = oracle.ChainReference()
     for name, kw in (("std", {}), ("inf", dict(n_regions=6, seed=62, with_inf=True))):
         mats, sites = G.sites(**kw)
         out[f"{name}_n_mats"] = np.array(len(mats))

@@ -75,7 +75,9 @@ def call_region(region, oracle, index=0):
         for h, evs in enumerate(overlapping):
             hits = [alleles.index(compatible(e)) if e[0] == begin else alleles.index(b"*") for e in evs]
             hap_allele[h] = max(hits, default=0)
-        lo, hi = (begin - 2) % U64, (loc_end + 2) % U64
+        # begin < 2: the reference's begin - 2 wraps and Interval's constructor throws
+        # (interval.hpp:26-31,82-83); the library cuts the window at the contig's first base
+        lo, hi = max(begin - 2, 0), (loc_end + 2) % U64
         keep = np.array([r for r, (rb, re_) in enumerate(zip(region["read_begin"], region["read_end"]))
                          if int(rb) % U64 < hi and lo < int(re_) % U64], np.int32)
         gl, gi, gq = oracle.site(L, keep, hap_allele, len(alleles))

@@ -6,7 +6,9 @@ C++ program, against the same chain on the reference's own kernels compiled
 from its sources (oracle/_ref) plus the oracle's restated filter and genotyper
 loops. Offsets, CIGARs, kept reads, likelihood matrices, genotype likelihoods,
 genotypes and qualities must all be bit-identical (tests/cpp/region_pipeline.cpp).
-VCF parity with the reference binary stays unpinned (Boost and chrM absent)."""
+The reference's own filter and genotyper are pinned in tests/test_gpu_ref_pins.py.
+VCF parity with the reference binary stays unpinned (the assembler needs
+Boost.Graph, which is absent, and so is chrM)."""
 import json
 import os
 import subprocess

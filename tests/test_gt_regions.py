@@ -59,9 +59,11 @@ HAND = {
     "seven_alleles": (region(EIGHT[:2] + EIGHT[3:]),
                       [site(104, 105, [b"A", b"AA", b"AC", b"AG", b"AT", b"C", b"G"], [0, 5, 6, 1, 2, 3, 4])]),
     "outside_origin": (region([(b"AGGTTCGAAC", 0, "10M")], origin=(103, 106)), [site(104, 105, [b"A", b"T"], [0, 1])]),
-    # begin 1: begin - 2 wraps in unsigned arithmetic and no read is kept; begin 2 keeps as usual
-    "begin_below_2": (region([(b"AGTTACGTAC", 0, "10M")], pb=0, reads=((0, 50),)),
-                      [site(1, 2, [b"C", b"G"], [0, 1], keep=[]), site(2, 3, [b"G", b"T"], [0, 1], keep=[0])]),
+    # begin 0 and 1: the window [begin - 2, loc_end + 2) is cut at the contig's first base (the reference
+    # throws there): [0, 3) and [0, 4) are overlapped by [0,50) and [2,9), [3,9) only by the latter; begin 2 as usual
+    "begin_below_2": (region([(b"CGTTACGTAC", 0, "10M")], pb=0, reads=((0, 50), (2, 9), (3, 9), (4, 9))),
+                      [site(0, 1, [b"A", b"C"], [0, 1], keep=[0, 1]), site(1, 2, [b"C", b"G"], [0, 1], keep=[0, 1, 2]),
+                       site(2, 3, [b"G", b"T"], [0, 1], keep=[0, 1, 2, 3])]),
     "zero_reads": (region([(b"ACGTTCGTAC", 0, "10M")], reads=()), [site(104, 105, [b"A", b"T"], [0, 1], keep=[])]),
 }
 

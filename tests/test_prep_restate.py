@@ -1,9 +1,9 @@
 """CPU: the restatement of filter_reads / hard_clip_reads (prep_restate.py) pinned
 to cases worked by hand from the reference's text (utils/read_clipper.hpp:32-91,
-utils/read_filter.hpp, sam/sam.hpp:69-72, sam/cigar.hpp:92-111). sam.hpp needs
-Boost, which is absent, so the headers cannot be compiled here: these pins are
-what stands between the restatement and a misreading of them. Coordinates are
-0-based begins (POS = begin + 1)."""
+utils/read_filter.hpp, sam/sam.hpp:69-72, sam/cigar.hpp:92-111). They say in
+words what the code does at its quirks; what holds the restatement to the
+headers themselves is tests/test_ref_pins.py, which compares it with the
+reference compiled in place. Coordinates are 0-based begins (POS = begin + 1)."""
 import prep_restate as PR
 
 SEQ = PR.make_seq
