@@ -7,7 +7,9 @@
 //   hc_sam_parse (kept on the device with the text, the parser's lock held
 //             until the picks are back)
 //   resolve:  contig_of per record, read back for the result
-//   buckets:  place, scan, scatter, sort over the concatenated positions
+//   buckets:  place, scan, scatter, sort over the concatenated positions (dense),
+//             or keys, a stable radix sort of (key, record) and the run table,
+//             sized by the records (HC_GENOME_SORTED_BUCKETS, genome_sort_kernels.hip)
 //   picks:    one wave per genome-wide window: count, scan, a small readback of
 //             the offsets and the error word, then write and the readback of the picks
 //   hc_call_window structs on the worker pool, `ref` aimed into the window's own contig
@@ -30,6 +32,7 @@
 
 #include "../../include/hc_genome.h"
 #include "genome_kernels.hpp"
+#include "genome_sort_kernels.hpp"
 #include "pool.hpp"
 #include "sam_engine.hpp"
 #include "sam_kernels.hpp"
@@ -63,11 +66,22 @@ struct hc_genome_result {
 namespace {
 
 // No stream of its own: the kernels run on the parser's, under the parser's lock.
-Buf g_tab, g_pos, g_win, g_picks, g_rec, g_htab{nullptr, 0, true}, g_hback{nullptr, 0, true}, g_hpicks{nullptr, 0, true},
+Buf g_tab, g_pos, g_sort, g_win, g_picks, g_rec, g_htab{nullptr, 0, true}, g_hback{nullptr, 0, true}, g_hpicks{nullptr, 0, true},
     g_hrec{nullptr, 0, true};
-Stage g_st({&g_tab, &g_pos, &g_win, &g_picks, &g_rec, &g_htab, &g_hback, &g_hpicks, &g_hrec}, false);
+Stage g_st({&g_tab, &g_pos, &g_sort, &g_win, &g_picks, &g_rec, &g_htab, &g_hback, &g_hpicks, &g_hrec}, false);
 
-constexpr uint32_t kKnownFlags = HC_CONTIG_F64 | HC_CONTIG_DEFAULT_MODE | HC_CONTIG_WANT_SITE_READS | HC_CONTIG_SKIP_UNPLACED;
+constexpr uint32_t kKnownFlags = HC_CONTIG_F64 | HC_CONTIG_DEFAULT_MODE | HC_CONTIG_WANT_SITE_READS | HC_CONTIG_SKIP_UNPLACED |
+                                 HC_GENOME_SORTED_BUCKETS;
+
+// HC_GENOME_BUCKETS, read per call: "sorted" sets HC_GENOME_SORTED_BUCKETS, "dense" or unset changes nothing.
+int buckets_from_env(uint32_t& flags)
+{
+    const char* e = std::getenv("HC_GENOME_BUCKETS");
+    if (!e || std::strcmp(e, "dense") == 0) return HC_PHMM_OK;
+    if (std::strcmp(e, "sorted") != 0) return fail(HC_PHMM_EINVAL, "HC_GENOME_BUCKETS is neither sorted nor dense");
+    flags |= HC_GENOME_SORTED_BUCKETS;
+    return HC_PHMM_OK;
+}
 
 int32_t batch_windows()
 {
@@ -203,15 +217,35 @@ int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const 
     if (rc) return rc;
     rc = reserve(g_hrec, rec_bytes, "genome caller record readback");
     if (rc) return rc;
+    // Dense: arrays over the concatenated positions. Sorted: nothing is sized by total_len.
+    const bool sorted = (flags & HC_GENOME_SORTED_BUCKETS) != 0;
+    const size_t n_rec = size_t(std::max(dev.n_records, 1));
     Carver pc;
     const size_t o_err = pc.take(sizeof(unsigned long long));
-    const size_t o_count = pc.take(sizeof(int32_t) * size_t(total_len));
-    const size_t o_cursor = pc.take(sizeof(int32_t) * size_t(total_len));
-    const size_t zero_bytes = pc.off;   // [err | count | cursor] are set in front of every call
-    const size_t o_first = pc.take(sizeof(int64_t) * (size_t(total_len) + 1));
-    const size_t o_bucket = pc.take(sizeof(int32_t) * size_t(std::max(dev.n_records, 1)));
-    const size_t o_scan = pc.take(std::max(hcsam::scan_work_bytes(total_len), hcsam::scan_work_bytes(n_windows)));
-    rc = reserve(g_pos, pc.off, "genome caller position workspace");
+    size_t o_count = 0, o_cursor = 0, zero_bytes = 0, o_first = 0, o_bucket = 0, o_scan = 0;
+    size_t o_key[2] = {0, 0}, o_index[2] = {0, 0}, o_hist = 0, o_hfirst = 0, o_rpos = 0, o_rfirst = 0;
+    const int64_t n_hist = int64_t(kSortDigits) * sort_tiles(dev.n_records);
+    if (!sorted) {
+        o_count = pc.take(sizeof(int32_t) * size_t(total_len));
+        o_cursor = pc.take(sizeof(int32_t) * size_t(total_len));
+        zero_bytes = pc.off;   // [err | count | cursor] are set in front of every call
+        o_first = pc.take(sizeof(int64_t) * (size_t(total_len) + 1));
+        o_bucket = pc.take(sizeof(int32_t) * n_rec);
+        o_scan = pc.take(std::max(hcsam::scan_work_bytes(total_len), hcsam::scan_work_bytes(n_windows)));
+        rc = reserve(g_pos, pc.off, "genome caller position workspace");
+    } else {
+        for (int k = 0; k < 2; ++k) {
+            o_key[k] = pc.take(sizeof(int64_t) * (n_rec + 1));
+            o_index[k] = pc.take(sizeof(int32_t) * n_rec);
+        }
+        o_rpos = pc.take(sizeof(int64_t) * n_rec);
+        o_rfirst = pc.take(sizeof(int64_t) * (n_rec + 1));
+        o_hist = pc.take(sizeof(int32_t) * size_t(n_hist));
+        o_hfirst = pc.take(sizeof(int64_t) * (size_t(n_hist) + 1));
+        o_scan = pc.take(std::max({hcsam::scan_work_bytes(n_hist), hcsam::scan_work_bytes(dev.n_records),
+                                   hcsam::scan_work_bytes(n_windows)}));
+        rc = reserve(g_sort, pc.off, "genome caller sort workspace");
+    }
     if (rc) return rc;
     Carver wc;
     const size_t o_np = wc.take(sizeof(int32_t) * size_t(n_windows));
@@ -233,13 +267,17 @@ int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const 
                           reinterpret_cast<const int32_t*>(g_tab.p + t.o_name),
                           reinterpret_cast<const uint8_t*>(g_tab.p + t.o_pool)};
     a.contig_of = reinterpret_cast<int32_t*>(g_rec.p);
-    a.err = reinterpret_cast<unsigned long long*>(g_pos.p + o_err);
-    a.count = reinterpret_cast<int32_t*>(g_pos.p + o_count);
-    a.cursor = reinterpret_cast<int32_t*>(g_pos.p + o_cursor);
-    int64_t* first = reinterpret_cast<int64_t*>(g_pos.p + o_first);
-    a.first = first;
-    a.bucket = reinterpret_cast<int32_t*>(g_pos.p + o_bucket);
-    int64_t* scan_work = reinterpret_cast<int64_t*>(g_pos.p + o_scan);
+    char* work = sorted ? g_sort.p : g_pos.p;
+    a.err = reinterpret_cast<unsigned long long*>(work + o_err);
+    int64_t* first = nullptr;
+    if (!sorted) {
+        a.count = reinterpret_cast<int32_t*>(g_pos.p + o_count);
+        a.cursor = reinterpret_cast<int32_t*>(g_pos.p + o_cursor);
+        first = reinterpret_cast<int64_t*>(g_pos.p + o_first);
+        a.first = first;
+        a.bucket = reinterpret_cast<int32_t*>(g_pos.p + o_bucket);
+    }
+    int64_t* scan_work = reinterpret_cast<int64_t*>(work + o_scan);
     a.n_picked = reinterpret_cast<int32_t*>(g_win.p + o_np);
     int64_t* win_first = reinterpret_cast<int64_t*>(g_win.p + o_wf);
     a.win_first = win_first;
@@ -251,18 +289,35 @@ int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const 
         HIP_TRY(st, hipStreamSynchronize(st));
         tr.mark("resolve");
     }
-    HIP_TRY(st, hipMemsetAsync(g_pos.p, 0, zero_bytes, st));
-    HIP_TRY(st, hipMemsetAsync(a.err, 0xFF, sizeof(unsigned long long), st));
-    HIP_TRY(st, launch_place(a, st));
-    HIP_TRY(st, hcsam::launch_scan(a.count, total_len, first, scan_work, st));
-    HIP_TRY(st, launch_scatter(a, st));
-    HIP_TRY(st, launch_sort(a, st));
+    GenomeSortArgs s{};
+    if (!sorted) {
+        HIP_TRY(st, hipMemsetAsync(g_pos.p, 0, zero_bytes, st));
+        HIP_TRY(st, hipMemsetAsync(a.err, 0xFF, sizeof(unsigned long long), st));
+        HIP_TRY(st, launch_place(a, st));
+        HIP_TRY(st, hcsam::launch_scan(a.count, total_len, first, scan_work, st));
+        HIP_TRY(st, launch_scatter(a, st));
+        HIP_TRY(st, launch_sort(a, st));
+    } else {
+        s.g = a;
+        for (int k = 0; k < 2; ++k) {
+            s.key[k] = reinterpret_cast<int64_t*>(g_sort.p + o_key[k]);
+            s.index[k] = reinterpret_cast<int32_t*>(g_sort.p + o_index[k]);
+        }
+        s.hist = reinterpret_cast<int32_t*>(g_sort.p + o_hist);
+        s.hist_first = reinterpret_cast<int64_t*>(g_sort.p + o_hfirst);
+        s.scan_work = scan_work;
+        s.run_pos = reinterpret_cast<int64_t*>(g_sort.p + o_rpos);
+        s.run_first = reinterpret_cast<int64_t*>(g_sort.p + o_rfirst);
+        s.passes = sort_passes(total_len);
+        HIP_TRY(st, hipMemsetAsync(a.err, 0xFF, sizeof(unsigned long long), st));
+        HIP_TRY(st, launch_sorted_buckets(s, st));
+    }
     if (tr.on) {
         HIP_TRY(st, hipStreamSynchronize(st));
         tr.mark("buckets");
     }
     // ---- the picks: their counts first, so that the lists take what they need and no more
-    HIP_TRY(st, launch_pick_count(a, st));
+    HIP_TRY(st, sorted ? launch_sorted_pick_count(s, st) : launch_pick_count(a, st));
     HIP_TRY(st, hcsam::launch_scan(a.n_picked, n_windows, win_first, scan_work, st));
     HIP_TRY(st, hipMemcpyAsync(g_hback.p + h_err, a.err, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(st, hipMemcpyAsync(g_hback.p + h_wf, win_first, sizeof(int64_t) * (size_t(n_windows) + 1), hipMemcpyDeviceToHost, st));
@@ -315,12 +370,16 @@ int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const 
     rc = reserve(g_hpicks, pick_bytes, "genome caller picks readback");
     if (rc) return rc;
     a.picked = reinterpret_cast<int32_t*>(g_picks.p);
+    s.g.picked = a.picked;
     if (total) {
-        HIP_TRY(st, launch_pick_write(a, st));
+        HIP_TRY(st, sorted ? launch_sorted_pick_write(s, st) : launch_pick_write(a, st));
         HIP_TRY(st, hipMemcpyAsync(g_hpicks.p, g_picks.p, pick_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(st, hipStreamSynchronize(st));
     }
     tr.mark("picks");
+    tr.count("sorted", sorted ? 1 : 0);
+    tr.count("sort_passes", sorted ? s.passes : 0);
+    tr.count("tile_bytes", int64_t(rec_bytes + pc.off + wc.off));   // asked of the record, position / sort and window workspaces
     const int32_t* hp = reinterpret_cast<const int32_t*>(g_hpicks.p);
     res.picked.assign(hp, hp + total);
     for (int32_t k : res.picked)
@@ -487,16 +546,18 @@ int check_name(const char* name, int32_t k)
 }  // namespace
 
 extern "C" int hc_genome_call(const uint8_t* sam, int64_t sam_len, const hc_genome_contig* contigs, int32_t n_contigs,
-                              int32_t region_size, int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags,
+                              int32_t region_size, int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags_in,
                               hc_genome_result** out)
 {
     std::lock_guard<std::mutex> lk(g_st.mu);
     return call_frame(out, nullptr, [&](hc_genome_result& res) -> int {
+        uint32_t flags = flags_in;
         if (sam_len < 0 || (sam_len && !sam)) return fail(HC_PHMM_EINVAL, "null sam / negative length");
         if (!contigs) return fail(HC_PHMM_EINVAL, "null contigs");
         if (n_contigs < 1) return fail(HC_PHMM_EINVAL, "n_contigs below 1");
         if (n_contigs > HC_GENOME_MAX_CONTIGS) return fail(HC_PHMM_EINVAL, "more than " + std::to_string(HC_GENOME_MAX_CONTIGS) + " contigs");
         if (flags & ~kKnownFlags) return fail(HC_PHMM_EINVAL, "unknown flags");
+        if (int rc = buckets_from_env(flags)) return rc;
         if (pick_mode != HC_CONTIG_PICK_SEEDED && pick_mode != HC_CONTIG_PICK_FIRST) return fail(HC_PHMM_EINVAL, "unknown pick mode");
         if (region_size < 1) return fail(HC_PHMM_EINVAL, "region_size below 1");
         if (padding_size < 0 || padding_size > region_size) return fail(HC_PHMM_EINVAL, "padding_size outside 0 .. region_size");

@@ -105,6 +105,10 @@ struct Trace {
         std::snprintf(tmp, sizeof(tmp), " %s=%.3f", what, x);
         line += tmp;
     }
+    void count(const char* what, long long x)   // a whole number, printed as one
+    {
+        if (on) line += std::string(" ") + what + "=" + std::to_string(x);
+    }
     ~Trace()
     {
         if (on) std::fprintf(stderr, "%s%s\n", prefix, line.c_str());

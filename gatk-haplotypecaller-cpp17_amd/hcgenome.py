@@ -9,6 +9,14 @@ first_window, n_windows, n_records = the records whose RNAME is its name),
 ``contig_of`` in ``sam`` (per record the table index of its RNAME, or -1).
 Every contig's picks use the same seed.
 
+``sorted_buckets=True`` sets HC_GENOME_SORTED_BUCKETS: the buckets come from a
+sort sized by the records, not from arrays over every base of the table; the
+result is the same in every field. ``HC_GENOME_BUCKETS=sorted`` in the
+environment does the same for a caller that cannot pass the argument.
+``windows=`` (an iterable of genome-wide window indices) makes ``results`` and
+``call_genome`` read back those windows only, in that order, where a table has
+millions of them; the default is every window.
+
 ``read_fasta(text)`` reads every record of a FASTA text as the reference's
 operator>> (fasta/fasta.hpp:23-46) reads one: [(name, upper-cased sequence)].
 
@@ -31,6 +39,7 @@ HEADER = hcphmm.HEADER.replace("hc_pairhmm.h", "hc_genome.h")
 MAX_NAME_LEN = 255
 PICKS = hccontig.PICKS
 SKIP_UNPLACED = hccontig.SKIP_UNPLACED
+SORTED_BUCKETS = 512
 
 
 class GenomeError(hcbind.Error):
@@ -111,7 +120,7 @@ class Prepared:
     """The arguments of a call, built once (timing tools time run() alone)."""
 
     def __init__(self, sam, contigs, region_size=245, padding_size=85, seed=0, pick="seeded", skip_unplaced=False,
-                 use_double=None, want_site_reads=False):
+                 use_double=None, want_site_reads=False, sorted_buckets=False):
         self.sam = bytes(sam)
         self.names = [n.encode("latin-1") if isinstance(n, str) else bytes(n) for n, _ in contigs]
         self.refs = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for _, r in contigs]
@@ -121,7 +130,7 @@ class Prepared:
         self.n = len(contigs)
         self.region_size, self.padding_size, self.seed, self.pick = region_size, padding_size, seed, PICKS[pick]
         self.flags = (hcregion.flags_of(want_site_reads=want_site_reads, use_double=use_double)
-                      | (SKIP_UNPLACED if skip_unplaced else 0))
+                      | (SKIP_UNPLACED if skip_unplaced else 0) | (SORTED_BUCKETS if sorted_buckets else 0))
 
     def run(self):
         """One hc_genome_call; returns the handle (free it with free())."""
@@ -135,7 +144,7 @@ class Prepared:
         lib().hc_genome_result_free(h)
 
 
-def results(h, names):
+def results(h, names, windows=None):
     L = lib()
     text, length, nw, nc = C.c_void_p(), C.c_int64(), C.c_int32(), C.c_int32()
     _check(L.hc_genome_result_vcf(h, C.byref(text), C.byref(length), C.byref(nw), C.byref(nc)))
@@ -145,7 +154,7 @@ def results(h, names):
         _check(L.hc_genome_result_contig(h, c, C.byref(fw), C.byref(n), C.byref(nr)))
         contigs.append(dict(name=names[c], first_window=fw.value, n_windows=n.value, n_records=nr.value))
     wins = []
-    for w in range(nw.value):
+    for w in (range(nw.value) if windows is None else windows):
         b = [C.c_int64() for _ in range(4)]
         ct, rl, npk, st, ast, k, nh = (C.c_int32() for _ in range(7))
         pk = _i32p()
@@ -168,10 +177,11 @@ def results(h, names):
 
 
 def call_genome(sam, contigs, region_size=245, padding_size=85, seed=0, pick="seeded", skip_unplaced=False,
-                use_double=None, want_site_reads=False):
-    p = Prepared(sam, contigs, region_size, padding_size, seed, pick, skip_unplaced, use_double, want_site_reads)
+                use_double=None, want_site_reads=False, sorted_buckets=False, windows=None):
+    p = Prepared(sam, contigs, region_size, padding_size, seed, pick, skip_unplaced, use_double, want_site_reads,
+                 sorted_buckets)
     h = p.run()
     try:
-        return results(h, [n.decode("latin-1") for n in p.names])
+        return results(h, [n.decode("latin-1") for n in p.names], windows)
     finally:
         p.free(h)

@@ -43,14 +43,37 @@
  * space, two equal names (the message names both indices), more than 2^31 - 1
  * windows in total.
  *
- * The device workspace is that of hc_contig.h with the sum of all ref_len in
- * the place of ref_len: 24 bytes per base of the table, 4 per record, 4 per
- * picked read, and the table itself (about 74 GB for a human genome of 3.1
- * Gbases: call it chromosome by chromosome, or with the contigs that have
- * reads, where that does not fit). `ref` is used as it is: upper-case it first.
- * No CPU fallback. Calls are serialised under the genome caller's own lock; a
- * failed call leaves every engine usable. HC_GENOME_TRACE=1 prints the host
- * wall clock of the phases on stderr.
+ * The device workspace. Besides the SAM text (which has to fit the device), the
+ * table itself, 4 bytes per record, 4 per picked read and 12 per window (a
+ * human genome at region 245 has 12.6 M windows), the buckets take
+ *   dense (the default): that of hc_contig.h with the sum of all ref_len in the
+ *     place of ref_len, 16 bytes per base of the table (two counters and an
+ *     offset): about 50 GB for a human genome of 3.1 Gbases, with the memsets
+ *     and a scan over every base;
+ *   sorted (HC_GENOME_SORTED_BUCKETS): nothing per base. A stable radix sort of
+ *     (off[contig] + POS - 1, record index), 8 bits per pass,
+ *     ceil(bits(sum of ref_len) / 8) passes, and a table of the runs of equal
+ *     keys: at most 42 bytes per record, a few hundred MB for an exome, a panel
+ *     or a low-coverage sample on the full GRCh38 table. The sum of all ref_len
+ *     is bounded by 2^63 only; the record count stays the parser's int32.
+ * Both give the same result in every field and byte, errors and their messages
+ * included; within a position the reads are in file order either way. Dense
+ * stays the default: the choice is the caller's, through the flag, or through
+ * the environment for a caller that cannot pass one: HC_GENOME_BUCKETS=sorted
+ * acts as the flag, =dense or unset changes nothing (the flag wins over dense),
+ * any other value is HC_PHMM_EINVAL naming the variable. It is read per call.
+ * hc_contig_call (hc_contig.h) keeps its dense buckets and refuses the flag.
+ * Where the dense workspace does not fit and the sorted one is not wanted: call
+ * chromosome by chromosome, or with the contigs that have reads.
+ *
+ * `ref` is used as it is: upper-case it first; a contig no window of which has
+ * reads is never read. FASTA reading stays on the host. No CPU fallback. Calls
+ * are serialised under the genome caller's own lock; a failed call leaves every
+ * engine usable. HC_GENOME_TRACE=1 prints one line "[hc_genome] key=value ..."
+ * per call on stderr: the host wall clock of the phases, the counts, and
+ * sorted=0|1, sort_passes=N, tile_bytes=B (the device bytes this call asked of
+ * the record, position or sort, and window workspaces together; the grow-only
+ * buffers may hold more).
  */
 #ifndef HC_GENOME_H
 #define HC_GENOME_H
@@ -66,6 +89,10 @@ extern "C" {
 #define HC_GENOME_MAX_NAME_LEN 255
 #define HC_GENOME_MAX_CONTIGS 4194304 /* the name pool and the table are indexed with 32 bits */
 
+/* A flag of hc_genome_call beside the HC_CONTIG_* ones: buckets by a sort sized
+ * by the records ("The device workspace" above). Not a flag of hc_contig_call. */
+#define HC_GENOME_SORTED_BUCKETS 512u
+
 typedef struct hc_genome_contig {
     const char* name;    /* the CHROM text and the RNAME it answers to (NUL-terminated) */
     const uint8_t* ref;
@@ -74,7 +101,7 @@ typedef struct hc_genome_contig {
 
 typedef struct hc_genome_result hc_genome_result;
 
-/* One synchronous call. flags are HC_CONTIG_*, pick_mode HC_CONTIG_PICK_*.
+/* One synchronous call. flags are HC_CONTIG_* and HC_GENOME_SORTED_BUCKETS, pick_mode HC_CONTIG_PICK_*.
  * `sam` must stay as it is until the result is freed: the result's records
  * are views into it. The table and what it points to are read during the call
  * only. Release the result with hc_genome_result_free. All pointers the

@@ -22,6 +22,12 @@
 // contig's picks use the same seed. skip_unplaced also leaves out the reads
 // whose RNAME is no record of the FASTA file.
 //
+// sorted_buckets = true sets HC_GENOME_SORTED_BUCKETS (hc_genome.h, "The device
+// workspace"): buckets by a sort sized by the records in the place of arrays
+// over every base of the FASTA file, for a file with few reads on a large
+// table. The VCF is the same bytes. HC_GENOME_BUCKETS=sorted in the environment
+// does the same without a rebuild.
+//
 // Header-only and free of reference headers. Invalid input throws
 // std::invalid_argument, everything else std::runtime_error, with the
 // library's message.
@@ -48,6 +54,7 @@ public:
     std::uint64_t seed = 0;
     int pick_mode = HC_CONTIG_PICK_SEEDED;
     bool skip_unplaced = false;
+    bool sorted_buckets = false;
 
     // use_double: the PairHMM's per-instance mode, as hc::MI355XWindowCaller's.
     explicit MI355XGenomeCaller(int device = -1, bool use_double = false) : device_(device), use_double_(use_double) {}
@@ -69,7 +76,8 @@ public:
         if (table.size() > 0x7fffffffu) throw std::invalid_argument("hc_genome: too many FASTA records");
         check(hc_phmm_init(HC_PHMM_FLAG_KEEP_MODE, device_));   // device only: the mode goes with the call
         hc_genome_result* res = nullptr;
-        const uint32_t flags = (use_double_ ? HC_CONTIG_F64 : 0u) | (skip_unplaced ? HC_CONTIG_SKIP_UNPLACED : 0u);
+        const uint32_t flags = (use_double_ ? HC_CONTIG_F64 : 0u) | (skip_unplaced ? HC_CONTIG_SKIP_UNPLACED : 0u) |
+                               (sorted_buckets ? HC_GENOME_SORTED_BUCKETS : 0u);
         check(hc_genome_call(reinterpret_cast<const uint8_t*>(sam.data()), static_cast<int64_t>(sam.size()), table.data(),
                              static_cast<int32_t>(table.size()), static_cast<int32_t>(region_size),
                              static_cast<int32_t>(padding_size), seed, pick_mode, flags, &res));

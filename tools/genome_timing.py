@@ -151,6 +151,74 @@ def shape(windows, n_contigs, a):
     return out
 
 
+def both_modes(table, text, a, sparse=False):
+    """Dense and sorted in turn on one text and table."""
+    modes = {m: hcgenome.Prepared(text, table, a.region, a.padding, seed=a.seed, sorted_buckets=(m == "sorted"))
+             for m in ("dense", "sorted")}
+    vcf, n_windows, n_records = {}, 0, 0
+    for m, g in modes.items():   # the warm-up, and the bytes both must give
+        h = g.run()
+        t_, n_, w_ = C.c_void_p(), C.c_int64(), C.c_int32()
+        hcgenome.lib().hc_genome_result_vcf(h, C.byref(t_), C.byref(n_), C.byref(w_), None)
+        r_ = C.c_int32()
+        hcgenome.lib().hc_genome_result_sam(h, None, None, C.byref(r_), None, None, None)
+        vcf[m], n_windows, n_records = C.string_at(t_, n_.value), w_.value, r_.value
+        g.free(h)
+    ts = {m: [] for m in modes}
+    for _ in range(a.reps):
+        for m, g in modes.items():
+            ts[m] += timed(lambda: g.free(g.run()), 1)
+    out = dict(contigs=len(table), windows=n_windows, table_bases=sum(len(r) for _, r in table), text_bytes=len(text),
+               records=n_records, vcf_bytes=len(vcf["dense"]), sorted_vcf_equals_dense=bool(vcf["dense"] == vcf["sorted"]))
+    for m, g in modes.items():
+        tr = traced(lambda: g.free(g.run()), a.trace_reps)
+        out[m] = dict(genome_call_ms=stats(ts[m]), buckets_ms=tr["took_ms"]["buckets"], picks_ms=tr["took_ms"]["picks"],
+                      tile_bytes=int(tr["marks"]["tile_bytes"]), sort_passes=int(tr["marks"]["sort_passes"]))
+    d, s = out["dense"]["genome_call_ms"], out["sorted"]["genome_call_ms"]
+    out["sorted_minus_dense_ms"] = round(s["median"] - d["median"], 3)
+    out["dense_spread_ms"] = round(d["max"] - d["min"], 3)
+    out["sorted_median_inside_dense_min_max"] = bool(d["min"] <= s["median"] <= d["max"])
+    if sparse:
+        out["dense_over_sorted"] = round(d["median"] / s["median"], 3)
+    return out
+
+
+def buckets_main(a):
+    import torch
+    bid = hcphmm.ensure_built()
+    hcphmm.init(0)
+    shapes = {}
+    wanted = lambda name: not a.only or name in a.only   # noqa: E731
+    for n in a.cuts:
+        if wanted(f"cut_{n}"):
+            table, text, _ = generate(a.windows, n, a.region, a.read_len, a.per_position, a.seed)
+            shapes[f"cut_{n}"] = both_modes(table, text, a)
+            print(f"cut_{n}: done", file=sys.stderr, flush=True)
+    name = f"one_window_x{a.small_contigs}"
+    if a.small_contigs and wanted(name):
+        table, text, _ = generate(a.small_contigs, a.small_contigs, a.region, a.read_len, a.per_position, a.seed)
+        shapes[name] = both_modes(table, text, a)
+    name = f"sparse_filler_2p{a.filler_bits}"
+    if a.filler_bits and wanted(name):
+        table, text, _ = generate(a.windows, 1, a.region, a.read_len, a.per_position, a.seed)
+        shapes[name] = both_modes([("chrFill", b"A" * (1 << a.filler_bits))] + table, text, a, sparse=True)
+    out = dict(workload=dict(region=a.region, padding=a.padding, read_len=a.read_len, reads_per_position=a.per_position,
+                             seed=a.seed, batch_windows=os.environ.get("HC_CONTIG_BATCH_WINDOWS", "512")),
+               reps=a.reps, trace_reps=a.trace_reps,
+               statistic="median, min, max of reps calls per mode, dense and sorted in turn, after one warm-up call of each, "
+                         "wall clock around the C calls, ms; phases: median of trace_reps traced calls",
+               shapes=shapes, device=torch.cuda.get_device_name(0), library=dict(kernel=bid["kernel"], lib=bid["lib"]))
+    write(a.out, out)
+
+
+def write(path, out):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=512)
@@ -163,8 +231,22 @@ def main():
     ap.add_argument("--seed", type=int, default=77)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--trace-reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "genome_timing.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--buckets", action="store_true", help="dense against sorted buckets, in turn")
+    ap.add_argument("--filler-bits", type=int, default=28, help="--buckets: the sparse shape's filler (0: leave it out)")
+    ap.add_argument("--only", nargs="*", default=[], help="--buckets: the shapes to run")
+    ap.add_argument("--merge", nargs="*", default=[], help="files of --buckets runs whose shapes go into --out")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "genome_sorted_timing.json" if a.buckets or a.merge else "genome_timing.json")
+    if a.merge:
+        parts = [json.load(open(f)) for f in a.merge]
+        for p in parts[1:]:
+            assert p["library"] == parts[0]["library"] and p["workload"] == parts[0]["workload"]
+            parts[0]["shapes"].update(p["shapes"])
+        return write(a.out, parts[0])
+    if a.buckets:
+        return buckets_main(a)
     import torch
     bid = hcphmm.ensure_built()
     hcphmm.init(0)
