@@ -537,7 +537,7 @@ __device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float
     float sumM = 0.f, sumX = 0.f;
     switch (bc) {
 #define HC_SEG_CASE(W) \
-    case W: run_seg_bc<float, W>(a.lut, ptab, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq); break;
+    case W: run_seg_bc<float, W>(a.lut, ptab, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq, w1); break;
         HC_SEG_WIDTHS(HC_SEG_CASE)
 #undef HC_SEG_CASE
     default: break;
@@ -579,10 +579,12 @@ __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
     // wave's first loads, so the fill overlaps the wave's descriptor loads
     // (small batches are one round of waves: every wave's start-up latency is
     // on the pass's critical path). The region also takes the quad table (10
-    // KB, rows of 128 bytes), which a wide wave whose qualities fit it writes
-    // over the pair table (run_seg_bc): 12.5 KB of LDS per wave with the match
-    // window, 12 waves per CU in 160 KiB.
-    __shared__ __attribute__((aligned(128))) float ptabs[kSegWPB][kPriorLdsLen];
+    // KB, rows of 256 bytes, each wave's 256-byte aligned: a row's base and
+    // the pattern bits are joined by an OR), which a wide wave whose qualities
+    // fit it writes over the pair table (run_seg_bc): 12.5 KB of LDS per wave
+    // with the match window, 12 waves per CU in 160 KiB.
+    __shared__ __attribute__((aligned(256))) float ptabs[kSegWPB][kPriorLdsLen];
+    static_assert(kPriorLdsLen * 4 % 256 == 0, "every wave's table 256-byte aligned");
     static_assert(kSegWPB * (kPriorLdsLen * 4 + 5 * 64 * 8) <= 160 * 1024 / 12 * kSegWPB, "12 waves per CU");
     const int n_waves = a.n_waves_dev ? __builtin_amdgcn_readfirstlane(*a.n_waves_dev) : a.n_waves;
     const int wib = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
@@ -637,7 +639,7 @@ __device__ __forceinline__ int slot_wave(const Seg64Args& a, const double* __res
     double sumM = 0.0, sumX = 0.0;
     switch (bc) {
 #define HC_SEG64_CASE(WI) \
-    case seg64_width(WI): run_seg_bc<double, seg64_width(WI)>(a.lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq); break;
+    case seg64_width(WI): run_seg_bc<double, seg64_width(WI)>(a.lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq, w1); break;
         HC_SEG64_CASE(0) HC_SEG64_CASE(1) HC_SEG64_CASE(2) HC_SEG64_CASE(3) HC_SEG64_CASE(4) HC_SEG64_CASE(5)
         HC_SEG64_CASE(6)
 #undef HC_SEG64_CASE

@@ -235,30 +235,37 @@ constexpr int kPtabMinWidth = 34;
 constexpr int kPtabAhead = 2;
 
 // The quad table: the same priors indexed by FOUR match bits, so one address
-// serves four columns (a shift and a v_and_or_b32 per four columns where the
-// pair table takes them per two). A quality row holds 16 patterns, 256 bytes,
-// laid out as two regions of float2 that share the address:
-//   region A [r][c] = priors of the group's first two columns (pattern bits 3, 2),
-//   region B [r][c] = priors of its last two (bits 1, 0), kQuadRegionB bytes
-//                     behind A: the second ds_read_b64 takes the address
-//                     register of the first and the DS immediate offset.
-// Rows are 128 bytes in each region, 32 of the 64 banks, so rows two apart
-// share their banks; the physical column is c = pattern ^ ((r >> 1) & 15),
-// which spreads the (skewed) patterns of lanes on such rows over all 16 bank
-// pairs (tools/lds_quad_model.py: 10.9 LDS cycles per read without, 6.2 with).
-// The XOR is applied to the row's two window words, once per row, with the
-// nibble replicated eight times.
+// and one 16-byte read (ds_read_b128) serve four columns, where the pair table
+// takes a shift, a v_and_or_b32 and a ds_read_b64 per two. A quality row holds
+// 16 patterns of float4, 256 bytes:
+//   tab[r][c] = priors of the group's columns 0, 1, 2, 3 (pattern bits 3 .. 0
+//               choose pm or px; the group's first column is the highest bit,
+//               as in the MSB-first window).
+// A row covers all 64 banks, so the row does not pick the banks, only the
+// 16-byte column slot does, and the skewed pattern distribution (match bits
+// at p = 0.25) piles the 16 lanes of a ds_read_b128 service group onto a few
+// slots. The physical column is c = pattern ^ (r & 15), which spreads lanes on
+// different rows over all 16 slots (tools/lds_quad_model.py: 19.9 LDS cycles
+// per four columns without, 11.6 with; two ds_read_b64 of 128-byte rows took
+// 12.5). The XOR is applied to the row's two window words, once per row, with
+// the nibble replicated eight times.
 // 128 such rows do not fit a wave's share of the LDS (12 waves per CU in
 // 160 KiB: 13 653 bytes, 2 560 of them the match window), so the table covers
 // kQuadRows consecutive qualities from the lowest of the wave's own reads
 // (quad_scan); a wave whose reads span more keeps the pair table. The quad
 // table lies over the pair table and the pm/px arrays (one region, fill_ptab
-// first for every wave, fill_qtab over it for a quad wave).
+// first for every wave, fill_qtab over it for a quad wave); the region is
+// 256-byte aligned, so a row's base | (pattern bits << 4) is an address.
 // HC_PTAB_NO_QUAD (EXTRA_DEV_FLAGS, A/B builds): every width keeps the pair table.
+// HC_QUAD_NO_SWIZZLE (likewise): the physical column is the pattern.
+#ifdef HC_QUAD_NO_SWIZZLE
+constexpr bool kQuadSwizzle = false;
+#else
+constexpr bool kQuadSwizzle = true;
+#endif
 constexpr int kQuadRows = 40;                          // Phred 2..41 spans exactly 40
-constexpr int kQuadRowBytes = 128;
-constexpr int kQuadRegionB = kQuadRows * kQuadRowBytes;   // byte offset of region B from A
-constexpr int kQuadLen = 2 * kQuadRegionB / 4;         // floats of the quad table
+constexpr int kQuadRowBytes = 256;
+constexpr int kQuadLen = kQuadRows * kQuadRowBytes / 4;   // floats of the quad table
 // Widths whose quad form fits the register budget (168 VGPRs, no scratch).
 #ifdef HC_PTAB_NO_QUAD
 constexpr int kQuadMinWidth = 1 << 30, kQuadMaxWidth = 0;
@@ -287,11 +294,11 @@ __device__ __forceinline__ int wave_min(int v)
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-// Rows r = 4t + lane / 16 (t = 0..9), pattern p = lane & 15: one float2 store
-// per region and row. Qualities past 127 (a window that starts above 88) are
-// rows no read selects. pm and px come from the arrays behind the pair table
-// (fill_ptab), which this table overwrites: every lane reads all of its own
-// before the wave's first store.
+// Rows r = 4t + lane / 16 (t = 0..9), pattern p = lane & 15: one 16-byte store
+// per row. Qualities past 127 (a window that starts above 88) are rows no read
+// selects. pm and px come from the arrays behind the pair table (fill_ptab),
+// which this table overwrites: every lane reads all of its own before the
+// wave's first store.
 __device__ __forceinline__ void fill_qtab(float* tab, int lane, int qmin)
 {
     const int p = lane & 15;
@@ -307,10 +314,9 @@ __device__ __forceinline__ void fill_qtab(float* tab, int lane, int qmin)
     for (int t = 0; t < kQuadRows / 4; ++t) {
         const int r = 4 * t + (lane >> 4);
         const float pm = pmr[t], px = pxr[t];
-        const int c = p ^ ((r >> 1) & 15);
-        float2* d = reinterpret_cast<float2*>(tab + r * (kQuadRowBytes / 4) + c * 2);
-        d[0] = make_float2((p & 8) ? pm : px, (p & 4) ? pm : px);
-        d[kQuadRegionB / 8] = make_float2((p & 2) ? pm : px, (p & 1) ? pm : px);
+        const int c = kQuadSwizzle ? p ^ (r & 15) : p;
+        *reinterpret_cast<float4*>(tab + r * (kQuadRowBytes / 4) + c * 4) =
+            make_float4((p & 8) ? pm : px, (p & 4) ? pm : px, (p & 2) ? pm : px, (p & 1) ? pm : px);
     }
 }
 
@@ -322,8 +328,8 @@ __device__ __forceinline__ void quad_row(uint32_t tab_lds, uint32_t qmin, uint32
 {
     const uint32_t r = min(uint32_t(row_q(w)) - qmin, uint32_t(kQuadRows - 1));
     base = tab_lds + r * kQuadRowBytes;
-    const uint32_t n6 = __umul24((r >> 1) & 15u, 0x111111u);   // six copies, full rate
-    rep = n6 | (n6 << 8);
+    const uint32_t n6 = __umul24(r & 15u, 0x111111u);   // six copies, full rate
+    rep = kQuadSwizzle ? n6 | (n6 << 8) : 0u;
 }
 
 // A row's table base (and, QUAD, its swizzle) from its row word.
@@ -336,68 +342,67 @@ __device__ __forceinline__ void tab_row(uint32_t tab_lds, uint32_t qmin, uint32_
         base = ptab_row(tab_lds, w);
 }
 
-// Address of column group G (block columns 4G .. 4G+3) of a row: the four
-// (swizzled) window bits at bits 6:3 of the row's 128-byte-aligned base. The
+// The priors of column group G (block columns 4G .. 4G+3) of a row: the four
+// (swizzled) window bits at bits 7:4 of the row's 256-byte-aligned base. The
 // last group of a width that is no multiple of 4 takes its low two bits from
-// the window's next columns; region A's entries do not depend on them.
+// the window's next columns; an entry's .x and .y do not depend on them.
+typedef float float4v __attribute__((ext_vector_type(4)));
+using lds_cfloat4 = const __attribute__((address_space(3))) float4v;
 template <int G>
-__device__ __forceinline__ uint32_t quad_addr(uint32_t base, const uint2& m)
+__device__ __forceinline__ float4 quad_read(uint32_t base, const uint2& m)
 {
     constexpr int sh = 28 - 4 * (G & 7);
     const uint32_t w = (G >> 3) ? m.y : m.x;
     uint32_t bits;
-    if constexpr (sh >= 3)
-        bits = w >> (sh - 3);
+    if constexpr (sh >= 4)
+        bits = w >> (sh - 4);
     else
-        bits = w << (3 - sh);
-    return base | (bits & 0x78u);
+        bits = w << (4 - sh);
+    const float4v v = *reinterpret_cast<lds_cfloat4*>(base | (bits & 0xf0u));
+    return make_float4(v.x, v.y, v.z, v.w);
 }
-// Region REG (0: A, 1: B) at a group's address.
-template <int REG>
-__device__ __forceinline__ float2 quad_read(uint32_t addr)
+
+// What one table read gives and a row keeps a ring of: entry E of a row is a
+// pair of columns' priors (pair table) or a group of four (quad table).
+template <bool QUAD> using TabEnt = std::conditional_t<QUAD, float4, float2>;
+template <bool QUAD, int E>
+__device__ __forceinline__ TabEnt<QUAD> tab_ent(uint32_t base, const uint2& mrow)
 {
-    const float2v v = *reinterpret_cast<lds_cfloat2*>(addr + REG * kQuadRegionB);
-    return make_float2(v.x, v.y);
+    if constexpr (QUAD)
+        return quad_read<E>(base, mrow);
+    else
+        return ptab_pair<E>(base, mrow);
 }
+__device__ __forceinline__ float ent_el(const float2& v, int e) { return e ? v.y : v.x; }
+__device__ __forceinline__ float ent_el(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 
 // Column J of one row, fp32 EQ path with table priors: `cell`'s EQ arithmetic
-// in the same order. pr is a ring of D pairs: on entry to an even column
-// J = 2p it holds pairs p .. p+D-1. The column takes its successor's prior,
-// pair p's second element and last use, and then issues the read of pair p+D
-// into pair p's registers, 2D - 1 columns ahead of its first use. The first
-// scheduling barrier keeps that multiply ahead of the read (behind it, the
-// read needs registers of its own), the second lets VALU work through and
-// keeps the LDS reads where they are (hoisted to the row's start they take
-// two registers each, sunk to their use the wave waits on every one).
-// QUAD: pair P is region P & 1 at the address of group P >> 1; the address
-// (qa) is formed with the read of a group's first pair and held for the
-// second, two columns later (mrow: the swizzled window).
-template <bool QUAD, int P>
-__device__ __forceinline__ float2 tab_pair(uint32_t base, const uint2& mrow, uint32_t& qa)
-{
-    if constexpr (QUAD) {
-        if constexpr ((P & 1) == 0) qa = quad_addr<P / 2>(base, mrow);
-        return quad_read<P & 1>(qa);
-    } else {
-        return ptab_pair<P>(base, mrow);
-    }
-}
-
+// in the same order. An entry holds the priors of N columns (pair table 2,
+// quad table 4) and pr is a ring of D = 2 entries: on entry to column J = N e
+// it holds entries e and e + 1. The column N e + N - 2 takes its successor's
+// prior, entry e's last element and last use, and then issues the read of
+// entry e + 2 into entry e's registers, 2N - 1 columns ahead of its first use
+// (pairs 3, groups 5). The first scheduling barrier keeps that multiply ahead
+// of the read (behind it, the read needs registers of its own), the second
+// lets VALU work through and keeps the LDS reads where they are (hoisted to
+// the row's start they take an entry's registers each, sunk to their use the
+// wave waits on every one).
+// QUAD: mrow is the swizzled window. A width with BC % 4 == 2 ends in a half
+// group: its read takes 16 bytes and the cells use .x and .y.
 template <int BC, int J, bool SUM, int D, bool QUAD>
 __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float M, float& Ml, float& Yl,
-                                         float2 (&pr)[D], uint32_t base, const uint2& mrow, uint32_t& qa,
+                                         TabEnt<QUAD> (&pr)[D], uint32_t base, const uint2& mrow,
                                          const RowConst<float>& k, float& sumM, float& sumX)
 {
+    constexpr int N = QUAD ? 4 : 2;           // columns per entry
+    constexpr int NE = (BC + N - 1) / N;      // entries of a row
     if constexpr (J < BC) {
         float Mn = M;
-        if constexpr (J + 1 < BC) {
-            const float2& q = pr[((J + 1) / 2) % D];
-            Mn = Tt[J] * (((J + 1) & 1) ? q.y : q.x);
-        }
-        if constexpr ((J & 1) == 0 && J / 2 + D < BC / 2) {
+        if constexpr (J + 1 < BC) Mn = Tt[J] * ent_el(pr[((J + 1) / N) % D], (J + 1) % N);
+        if constexpr (J % N == N - 2 && J / N + D < NE) {
             constexpr int kNoDs = 0x2 | 0x4 | 0x10 | 0x20 | 0x40;   // VALU, SALU and VMEM may cross; DS may not
             __builtin_amdgcn_sched_barrier(0);
-            pr[(J / 2 + D) % D] = tab_pair<QUAD, J / 2 + D>(base, mrow, qa);
+            pr[(J / N + D) % D] = tab_ent<QUAD, J / N + D>(base, mrow);
             __builtin_amdgcn_sched_barrier(kNoDs);
         }
         const float Xc = X[J];
@@ -411,7 +416,7 @@ __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float 
         X[J] = Mx + Xc * k.xx;
         Ml = Mx;
         Yl = Y;
-        cell_tab<BC, J + 1, SUM, D, QUAD>(Tt, X, Mn, Ml, Yl, pr, base, mrow, qa, k, sumM, sumX);
+        cell_tab<BC, J + 1, SUM, D, QUAD>(Tt, X, Mn, Ml, Yl, pr, base, mrow, k, sumM, sumX);
     }
 }
 
@@ -643,7 +648,7 @@ __device__ __forceinline__ void fill_window(uint2* __restrict__ mt, int lane, co
 template <typename T, int BC, bool CG, bool EQ, bool QUAD = false>
 __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __restrict__ slut, const SegSteps& st,
                                         int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
-                                        uint2* __restrict__ mt, uint32_t qmin = 0)
+                                        uint2* __restrict__ mt, uint32_t w1, uint32_t qmin = 0)
 {
     constexpr int PD = seg_prefetch<T, BC>();
     constexpr bool TAB = std::is_same<T, float>::value && CG && EQ && BC >= kPtabMinWidth;
@@ -669,7 +674,14 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     // P = (k-1) mod PD, for every lane at every step; the loads are issued
     // unconditionally so that each path has the same outstanding loads and
     // the wait for a word is the one PD steps after its load.
-    uint32_t wc = row_word(cx, 0);
+    // Row 1's word as the caller loaded it (w1). Loaded again here, its 64-bit
+    // address stays live from the wave's prologue to the last path of the
+    // width that loads it, through the step loops of the paths before: the
+    // two registers the widest quad block does not have. Opaque, so that no
+    // field of it is shared with the caller's uses of w1 (row0_t) and kept
+    // from there to here (it was spilled).
+    uint32_t wc = w1;
+    asm volatile("" : "+v"(wc));
     uint32_t wq[PD];
 #pragma unroll
     for (int P = 0; P < PD; ++P) wq[P] = row_word(cx, min(max(P + 2 - s, 1), R) - 1);
@@ -677,17 +689,18 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     row_const<T>(lut, wc, row_word(cx, min(2, R) - 1), k);
     uint2 mrow = mt[k.rc * 64 + lane];
     // TAB: ptab's LDS address, the coming row's table base and its first
-    // pair, read at the end of the step before (here: row 1's).
+    // entry (pair, or QUAD group of four), read at the end of the step before
+    // (here: row 1's).
     // QUAD: mrow is the swizzled window (the cells of a table row do not
-    // consume it), qa the address of the group being read.
-    uint32_t ptab_lds = 0, base = 0, qa = 0;
-    float2 pr0 = make_float2(0.f, 0.f);
+    // consume it).
+    uint32_t ptab_lds = 0, base = 0;
+    TabEnt<QUAD> pr0{};
     if constexpr (TAB) {
         ptab_lds = lds_addr(slut);
         uint32_t rep = 0;
         tab_row<QUAD>(ptab_lds, qmin, wc, base, rep);
         if constexpr (QUAD) mrow = make_uint2(mrow.x ^ rep, mrow.y ^ rep);
-        pr0 = tab_pair<QUAD, 0>(base, mrow, qa);
+        pr0 = tab_ent<QUAD, 0>(base, mrow);
     }
     // A pair's last block (and any lane past it) hands zeros to the lane on its
     // right, so a group's first lane needs no select: it receives Y = 0 entering
@@ -755,14 +768,14 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
             T Ml = T(0), Yl = Yl0;
             if constexpr (TAB) {
                 constexpr int D = kPtabAhead;
-                float2 pr[D];
+                constexpr int NE = QUAD ? (BC + 3) / 4 : NP;   // table entries of a row
+                TabEnt<QUAD> pr[D];
                 pr[0] = pr0;
-                // QUAD: qa is still pr0's address (group 0), formed at the last step's end.
-                for_phases<1, (D < NP ? D : NP)>([&](auto p) {
-                    pr[decltype(p)::value] = tab_pair<QUAD, decltype(p)::value>(base, mrow, qa);
+                for_phases<1, (D < NE ? D : NE)>([&](auto p) {
+                    pr[decltype(p)::value] = tab_ent<QUAD, decltype(p)::value>(base, mrow);
                 });
                 const float M0 = Tdiag * pr0.x;
-                cell_tab<BC, 0, SUM, D, QUAD>(Tt, X, M0, Ml, Yl, pr, base, mrow, qa, k, sumM, sumX);
+                cell_tab<BC, 0, SUM, D, QUAD>(Tt, X, M0, Ml, Yl, pr, base, mrow, k, sumM, sumX);
             } else {
                 const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);   // bit 31 of mrow.x first
                 cell<T, BC, 0, BC, SUM, EQ>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
@@ -784,7 +797,7 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
                 asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base));
                 mrow = mt[mo];
             }
-            pr0 = tab_pair<QUAD, 0>(base, mrow, qa);
+            pr0 = tab_ent<QUAD, 0>(base, mrow);
             wq[P] = row_word(cx, ridx);
         } else if constexpr (CG) {
             // Unconditional (no register moves for a conditional update): a
@@ -858,7 +871,7 @@ __device__ __forceinline__ void quad_scan(const LaneCtx& cx, int s, int nb, int&
 template <typename T, int BC>
 __device__ __forceinline__ void run_seg_bc(const T* __restrict__ lut, const T* __restrict__ slut, const SegSteps& st,
                                            int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
-                                           uint2* __restrict__ mt, bool wave_eq)
+                                           uint2* __restrict__ mt, bool wave_eq, uint32_t w1)
 {
     if constexpr (quad_width<T, BC>()) {
         // slut is the wave's prior region, writable: the quad table goes over
@@ -869,15 +882,15 @@ __device__ __forceinline__ void run_seg_bc(const T* __restrict__ lut, const T* _
             if (qmax - qmin < kQuadRows) {
                 fill_qtab(const_cast<T*>(slut), lane, qmin);
                 __builtin_amdgcn_wave_barrier();
-                run_seg<T, BC, true, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, uint32_t(qmin));
+                run_seg<T, BC, true, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, w1, uint32_t(qmin));
                 return;
             }
         }
     }
     if (wave_eq)
-        run_seg<T, BC, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt);
+        run_seg<T, BC, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, w1);
     else
-        run_seg<T, BC, false, false>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt);
+        run_seg<T, BC, false, false>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, w1);
 }
 
 // The fp64 rescue (intel_pairhmm.hpp:137-139) of the pairs this wave's fp32
@@ -903,7 +916,7 @@ __device__ __forceinline__ void rescue_one(const LaneArgs& a, const PairDesc pd,
     const double T0 = row0_t<double>(a.lut64, w1, H);
     const bool eq = read_eq(w1);
     double sM = 0.0, sX = 0.0;
-    run_seg_bc<double, bc>(a.lut64, a.lut64, st, lane, lane, cx, T0, sM, sX, mt, eq);
+    run_seg_bc<double, bc>(a.lut64, a.lut64, st, lane, lane, cx, T0, sM, sX, mt, eq, w1);
     if (lane == nb - 1) {
         const double r = sM + sX;
         if (a.rec) {   // record of slot rs: state and raw f64 (after the owner's store: same wave, program order)

@@ -26,8 +26,10 @@ shift of the window word, one v_and_or_b32 that puts its two bits into the
 row's table base (priced as the other three-source forms, 2 slots) and the
 ds_read_b64 of the pair, reported as "prior table (address)" and "prior table
 (LDS read)". The quad form (fill_qtab) forms that address once per four columns
-and reads twice at it, the second time with the DS immediate offset of region
-B: both reads count, and a loop with such reads is marked "quad"."""
+and reads 16 bytes at it (ds_read_b128, the priors of all four): a loop with
+such reads is marked "quad". (Round 11's quad form read twice at the address,
+ds_read_b64 with and without a DS immediate offset: both count as table reads,
+and such a loop is marked "quad" as well.)"""
 import collections
 import json
 import re
@@ -53,9 +55,9 @@ def operands(txt):
 
 def table_roles(ins):
     """Indices of the prior table's instructions in a loop: every v_and_or_b32,
-    the shift whose result it masks, and the ds_read_b64 at its address (the
-    quad form reads twice at one address, so the address stays a table address
-    until a VALU instruction overwrites its register)."""
+    the shift whose result it masks, and the ds_read_b64 or ds_read_b128 at its
+    address (the address stays a table address until a VALU instruction
+    overwrites its register: the two-read quad form read twice at it)."""
     addr, read = set(), set()
     shift_of, addr_regs = {}, set()
     for i, (op, t) in enumerate(ins):
@@ -66,7 +68,7 @@ def table_roles(ins):
                 addr.add(shift_of.pop(a[1]))
             addr_regs.add(a[0])
             continue
-        if op == "ds_read_b64" and a[1].split()[0] in addr_regs:   # "v165 offset:5120": the register
+        if op in ("ds_read_b64", "ds_read_b128") and a[1].split()[0] in addr_regs:   # "v165 offset:5120": the register
             read.add(i)
         if a and op.startswith("v_"):
             shift_of.pop(a[0], None)
@@ -182,12 +184,12 @@ def main():
             by_slot[r] += slots(op, t)
             if writes_vcc(op, t):
                 carry = op == "v_add_co_u32"
-        quad = any(op == "ds_read_b64" and "offset:" in t for i, (op, t) in enumerate(ins) if i in tab_read)
+        quad = any(op == "ds_read_b128" or "offset:" in t for i, (op, t) in enumerate(ins) if i in tab_read)
         rows.append(dict(kernel=lines[start].split(":")[0], loop=hdr, fp64=fp64, bc=bc, eq=eq, quad=quad, row_sums=sums, steps_per_iteration=steps,
                          s_nop_per_step=round(c["s_nop"] / steps, 2),
                          select_ops_per_step={k: round(c[k] / steps, 2) for k in
                                               ("v_add_co_u32", "v_cndmask_b32", "v_bfe_i32", "v_bitop3_b32")},
-                         table_ops_per_step={k: round(c[k] / steps, 2) for k in ("v_and_or_b32", "ds_read_b64")},
+                         table_ops_per_step={k: round(c[k] / steps, 2) for k in ("v_and_or_b32", "ds_read_b64", "ds_read_b128")},
                          cndmask_e64_per_step=round(sum(1 for op, t in ins if op == "v_cndmask_b32"
                                                         and t.split()[0].endswith("_e64")) / steps, 2),
                          arith_per_step=arith / steps,

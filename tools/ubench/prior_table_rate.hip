@@ -9,12 +9,13 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize \
 //         -fgpu-flush-denormals-to-zero prior_table_rate.hip -o prior_table_rate
 //   ./prior_table_rate            one JSON line per (form, BC, waves per SIMD)
-// Rows of the quad table (seg_common.hpp fill_qtab, one address per four
-// columns) with qualities drawn from 31 consecutive values as S2's: the pair
-// table at those qualities, the quad form as the kernel runs it (two
-// ds_read_b64 per group, swizzled), the same unswizzled, and a ds_read_b128
-// form (256-byte rows of 16 float4, column ^ (r & 15); a ring of two float4,
-// four more VGPRs than the two float2) that the kernel does not build.
+// Rows of the quad table (seg_common.hpp fill_qtab, one address and one
+// ds_read_b128 per four columns, 256-byte rows of 16 float4) with qualities
+// drawn from 31 consecutive values as S2's: the pair table at those qualities,
+// the quad form as the kernel runs it (fill_qtab, quad_row, quad_read,
+// cell_tab: column ^ (r & 15), a ring of two float4) and the same unswizzled.
+// (The two-read forms of round 11, two ds_read_b64 per group, are recorded in
+// profiles/quad_table_ubench.jsonl; the kernel no longer has them.)
 // LDS bank conflicts: the same binary under a counters-only profiler run
 // (SQ_INSTS_LDS, SQ_LDS_BANK_CONFLICT, SQ_LDS_IDX_ACTIVE per kernel name).
 #include <hip/hip_runtime.h>
@@ -33,46 +34,9 @@ __device__ __forceinline__ uint32_t lcg(uint32_t r) { return r * 1664525u + 1013
 __device__ __forceinline__ uint2 row_words(uint32_t r) { return make_uint2(r ^ (r >> 15), (r * 0x85ebca6bu) ^ (r >> 7)); }
 __device__ __forceinline__ uint32_t row_qual(uint32_t r) { return (r >> 12) & 127u; }
 
-enum Form { kPairWin = 0, kQuad, kQuadPlain, kQuad128 };
+enum Form { kPairWin = 0, kQuad, kQuadPlain };
 constexpr int kWinLo = 43, kWinSpan = 31;   // S2's qualities
 __device__ __forceinline__ uint32_t win_qual(uint32_t r) { return kWinLo + ((((r >> 12) & 1023u) * kWinSpan) >> 10); }
-
-// Group G of the b128 form: four window bits at bits 7:4 of a 256-byte row.
-template <int G>
-__device__ __forceinline__ float4 q128_read(uint32_t base, const uint2& m)
-{
-    constexpr int sh = 28 - 4 * (G & 7);
-    const uint32_t w = (G >> 3) ? m.y : m.x;
-    const uint32_t bits = sh >= 4 ? w >> (sh - 4) : w << (4 - sh);
-    typedef float float4v __attribute__((ext_vector_type(4)));
-    const float4v v = *reinterpret_cast<const __attribute__((address_space(3))) float4v*>(base | (bits & 0xf0u));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float q128_el(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-// cell_tab's arithmetic with a ring of two float4: group g's last use is at
-// column 4g + 2, which then reads group g + 2, five columns ahead of its first use.
-template <int BC, int J>
-__device__ __forceinline__ void cell_q128(float (&Tt)[BC], float (&X)[BC], float M, float& Ml, float& Yl,
-                                          float4 (&pr)[2], uint32_t base, const uint2& mrow, const RowConst<float>& k)
-{
-    if constexpr (J < BC) {
-        float Mn = M;
-        if constexpr (J + 1 < BC) Mn = Tt[J] * q128_el(pr[((J + 1) / 4) % 2], (J + 1) & 3);
-        if constexpr ((J & 3) == 2 && J / 4 + 2 < (BC + 3) / 4) {
-            __builtin_amdgcn_sched_barrier(0);
-            pr[(J / 4) % 2] = q128_read<J / 4 + 2>(base, mrow);
-            __builtin_amdgcn_sched_barrier(0x2 | 0x4 | 0x10 | 0x20 | 0x40);
-        }
-        const float Xc = X[J];
-        const float Mx = M * k.mx;
-        const float Y = (J == 0) ? Yl : (Ml + Yl * k.yy);
-        Tt[J] = (M * k.mm + Xc * k.g) + Y * k.g;
-        X[J] = Mx + Xc * k.xx;
-        Ml = Mx;
-        Yl = Y;
-        cell_q128<BC, J + 1>(Tt, X, Mn, Ml, Yl, pr, base, mrow, k);
-    }
-}
 
 template <int BC, int FORM>
 __global__ __launch_bounds__(64, 3) void quad_kernel(float* __restrict__ out, const float* __restrict__ lut, int rows,
@@ -85,19 +49,13 @@ __global__ __launch_bounds__(64, 3) void quad_kernel(float* __restrict__ out, co
     __builtin_amdgcn_wave_barrier();
     if constexpr (FORM == kQuad) {
         fill_qtab(lds, lane, kWinLo);
-    } else if constexpr (FORM != kPairWin) {
+    } else if constexpr (FORM == kQuadPlain) {   // fill_qtab's entries at column = pattern
         const int p = lane & 15;
         for (int t = 0; t < kQuadRows / 4; ++t) {
             const int r = 4 * t + (lane >> 4), q = kWinLo + r;
             const float pm = lut[kOffPm + q], px = lut[kOffPx + q];
-            const float a = (p & 8) ? pm : px, b = (p & 4) ? pm : px, c = (p & 2) ? pm : px, d = (p & 1) ? pm : px;
-            if constexpr (FORM == kQuadPlain) {
-                float2* e = reinterpret_cast<float2*>(lds + r * 32 + p * 2);
-                e[0] = make_float2(a, b);
-                e[kQuadRegionB / 8] = make_float2(c, d);
-            } else {
-                *reinterpret_cast<float4*>(lds + r * 64 + (p ^ (r & 15)) * 4) = make_float4(a, b, c, d);
-            }
+            *reinterpret_cast<float4*>(lds + r * (kQuadRowBytes / 4) + p * 4) =
+                make_float4((p & 8) ? pm : px, (p & 4) ? pm : px, (p & 2) ? pm : px, (p & 1) ? pm : px);
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -116,55 +74,32 @@ __global__ __launch_bounds__(64, 3) void quad_kernel(float* __restrict__ out, co
     k.rc = 0;
     uint32_t r = lcg(seed ^ ((blockIdx.x * 64u + lane) * 0x9e3779b9u));
     const uint32_t tab_lds = lds_addr(lds);
+    constexpr bool Q = FORM != kPairWin;
     uint2 mrow;
-    uint32_t base = 0, qa = 0;
-    float2 pr0 = make_float2(0.f, 0.f);
-    float4 pq0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    // The coming row's window, table base and first pair (the step's end in run_seg).
+    uint32_t base = 0;
+    TabEnt<Q> pr0{};
+    // The coming row's window, table base and first entry (the step's end in run_seg).
     auto next_row = [&](uint32_t rw) {
         const uint2 m = row_words(rw);
         const uint32_t q = win_qual(rw);
-        if constexpr (FORM == kPairWin) {
-            base = ptab_row(tab_lds, q);
-            mrow = m;
-            pr0 = ptab_pair<0>(base, mrow);
-        } else if constexpr (FORM == kQuad) {
-            uint32_t rep;
-            quad_row(tab_lds, kWinLo, q, base, rep);
-            mrow = make_uint2(m.x ^ rep, m.y ^ rep);
-            pr0 = tab_pair<true, 0>(base, mrow, qa);
-        } else if constexpr (FORM == kQuadPlain) {
-            base = tab_lds + min(q - kWinLo, uint32_t(kQuadRows - 1)) * kQuadRowBytes;
-            mrow = m;
-            pr0 = tab_pair<true, 0>(base, mrow, qa);
-        } else {
-            const uint32_t rr = min(q - kWinLo, uint32_t(kQuadRows - 1));
-            base = tab_lds + rr * 256u;
-            const uint32_t n6 = __umul24(rr & 15u, 0x111111u), rep = n6 | (n6 << 8);
-            mrow = make_uint2(m.x ^ rep, m.y ^ rep);
-            pq0 = q128_read<0>(base, mrow);
-        }
+        uint32_t rep = 0;
+        tab_row<Q>(tab_lds, kWinLo, q, base, rep);
+        if constexpr (FORM == kQuadPlain) rep = 0;
+        mrow = make_uint2(m.x ^ rep, m.y ^ rep);
+        pr0 = tab_ent<Q, 0>(base, mrow);
     };
     next_row(r);
     float sumM = 0.f, sumX = 0.f, y_in = 0.f, t_diag = 1.f;
     for (int i = 0; i < rows; ++i) {
         r = lcg(r);
         float Ml = 0.f, Yl = y_in;
-        if constexpr (FORM == kQuad128) {
-            float4 pr[2];
-            pr[0] = pq0;
-            if constexpr (BC > 4) pr[1] = q128_read<1>(base, mrow);
-            cell_q128<BC, 0>(Tt, X, t_diag * pq0.x, Ml, Yl, pr, base, mrow, k);
-        } else {
-            constexpr int D = kPtabAhead, NP = BC / 2;
-            constexpr bool Q = FORM != kPairWin;
-            float2 pr[D];
-            pr[0] = pr0;
-            for_phases<1, (D < NP ? D : NP)>([&](auto p) {
-                pr[decltype(p)::value] = tab_pair<Q, decltype(p)::value>(base, mrow, qa);
-            });
-            cell_tab<BC, 0, false, D, Q>(Tt, X, t_diag * pr0.x, Ml, Yl, pr, base, mrow, qa, k, sumM, sumX);
-        }
+        constexpr int D = kPtabAhead, NE = Q ? (BC + 3) / 4 : BC / 2;
+        TabEnt<Q> pr[D];
+        pr[0] = pr0;
+        for_phases<1, (D < NE ? D : NE)>([&](auto p) {
+            pr[decltype(p)::value] = tab_ent<Q, decltype(p)::value>(base, mrow);
+        });
+        cell_tab<BC, 0, false, D, Q>(Tt, X, t_diag * pr0.x, Ml, Yl, pr, base, mrow, k, sumM, sumX);
         next_row(r);
         y_in = y_next<true>(Ml, Yl, k.my, k.yy);
         t_diag = Tt[BC - 1];
@@ -202,7 +137,7 @@ __global__ __launch_bounds__(64, 3) void rate_kernel(float* __restrict__ out, co
     uint32_t r = lcg(seed ^ ((blockIdx.x * 64u + lane) * 0x9e3779b9u));
     uint2 mrow = row_words(r);
     const uint32_t ptab_lds = lds_addr(lds);
-    uint32_t base = ptab_row(ptab_lds, row_qual(r)), qa = 0;
+    uint32_t base = ptab_row(ptab_lds, row_qual(r));
     float2 pr0 = make_float2(0.f, 0.f);
     float pm = 0.f, px = 0.f;
     if constexpr (TAB) {
@@ -229,7 +164,7 @@ __global__ __launch_bounds__(64, 3) void rate_kernel(float* __restrict__ out, co
                 pr[decltype(p)::value] = ptab_pair<decltype(p)::value>(base, mrow);
             });
             const float M0 = t_diag * pr0.x;
-            cell_tab<BC, 0, false, D, false>(Tt, X, M0, Ml, Yl, pr, base, mrow, qa, k, sumM, sumX);
+            cell_tab<BC, 0, false, D, false>(Tt, X, M0, Ml, Yl, pr, base, mrow, k, sumM, sumX);
             mrow = m_n;
             base = ptab_row(ptab_lds, row_qual(r));
             pr0 = ptab_pair<0>(base, mrow);
@@ -294,8 +229,8 @@ void run_quad(float* out, const float* lut, int cus, int wps, int rows)
     hipEventElapsedTime(&ms, a, e);
     const hipError_t err = hipGetLastError();
     const double cells = double(grid) * 64 * BC * rows * reps;
-    static const char* names[] = {"pair table, 31 qualities", "quad table (2 x ds_read_b64, swizzled)",
-                                  "quad table (2 x ds_read_b64, plain)", "quad table (ds_read_b128, swizzled)"};
+    static const char* names[] = {"pair table, 31 qualities", "quad table (ds_read_b128, swizzled)",
+                                  "quad table (ds_read_b128, plain)"};
     printf("{\"form\": \"%s\", \"bc\": %d, \"waves_per_simd\": %d, \"rows\": %d, \"ms_per_launch\": %.4f, "
            "\"gcells_per_s\": %.1f, \"status\": \"%s\"}\n",
            names[FORM], BC, wps, rows, ms / reps, cells / (ms * 1e-3) / 1e9, hipGetErrorName(err));
@@ -344,11 +279,9 @@ int main()
         run_quad<64, kPairWin>(out, lut, cus, wps, rows);
         run_quad<64, kQuad>(out, lut, cus, wps, rows);
         run_quad<64, kQuadPlain>(out, lut, cus, wps, rows);
-        run_quad<64, kQuad128>(out, lut, cus, wps, rows);
         run_quad<48, kPairWin>(out, lut, cus, wps, rows);
         run_quad<48, kQuad>(out, lut, cus, wps, rows);
         run_quad<48, kQuadPlain>(out, lut, cus, wps, rows);
-        run_quad<48, kQuad128>(out, lut, cus, wps, rows);
     }
     hipFree(lut);
     hipFree(out);
