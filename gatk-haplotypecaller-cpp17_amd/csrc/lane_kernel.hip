@@ -187,11 +187,16 @@ __global__ __launch_bounds__(256, OCC) void phmm_lane_kernel(LaneArgs a)
 // Seg waves per workgroup (HC_SEG_WPB, A/B builds: EXTRA_DEV_FLAGS=-DHC_SEG_WPB=n).
 // A workgroup is dispatched when a CU has room for all its waves, so with 4
 // the slot a finished wave frees can wait for its workgroup's others (a 125k
-// pass spent 18 % of its SIMD time at 2 resident waves). One wave per
-// workgroup (each wave has its own LDS tables): S2 8.64 -> 8.59 ms, S1 and
-// the shard sizes unchanged (profiles/r04_wpb_ab.txt).
+// pass spent 18 % of its SIMD time at 2 resident waves): one wave per
+// workgroup, each with its own LDS tables, was 0.6 % faster on S2 in rounds 4
+// to 12 (profiles/r04_wpb_ab.txt). Since round 13 the prior tables are the
+// workgroup's, which is what leaves a wave the LDS for a spread match window
+// (phmm_seg_kernel), and a workgroup is four waves again, one per SIMD, three
+// workgroups to a CU. Three or six waves do not spread evenly over the four
+// SIMDs at three waves each: S2 5 447 and 3 757 GCUPS against 5 725 with four
+// (profiles/byte_window_ab.jsonl).
 #ifndef HC_SEG_WPB
-#define HC_SEG_WPB 1
+#define HC_SEG_WPB 4
 #endif
 constexpr int kSegWPB = HC_SEG_WPB;
 // ---------------------------------------------------------------------------
@@ -489,7 +494,8 @@ __device__ __forceinline__ void plan_rescue(const Seg64Args& a, int n, PlanLds& 
 }
 
 // One column-segmented wave (wid) of the fp32 pass.
-__device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float* __restrict__ ptab)
+__device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float* __restrict__ ptab,
+                                         const float* __restrict__ qtab)
 {
     // Lane id and the wave's LDS tables in forms the compiler can recompute
     // (mbcnt) or keep in SGPRs (wave-uniform): values live across the step
@@ -498,7 +504,9 @@ __device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float
     const unsigned long long t_start = a.timeline ? __builtin_amdgcn_s_memrealtime() : 0;
     const LaneWave wv = load_wave(a.waves, wid);
     const int bc = wv.ncols;
-    __shared__ uint2 mtab[kSegWPB][5 * 64];
+    // The wave's match window, packed (uint2 per read code and lane) or, for a
+    // quad wave, spread (16 bytes per read code and lane).
+    __shared__ __attribute__((aligned(256))) uint2 mtab[kSegWPB][kWindowBytes / 8];
     uint2* mt = mtab[__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6))];
     // Lane -> (group, block): group g's lanes start at the prefix sum of nb.
     int* gmap = reinterpret_cast<int*>(mt);   // 128 ints, used before the match table
@@ -537,7 +545,7 @@ __device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float
     float sumM = 0.f, sumX = 0.f;
     switch (bc) {
 #define HC_SEG_CASE(W) \
-    case W: run_seg_bc<float, W>(a.lut, ptab, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq, w1); break;
+    case W: run_seg_bc<float, W>(a.lut, ptab, st, lane, s, cx, T0, sumM, sumX, mt, wave_eq, w1, qtab); break;
         HC_SEG_WIDTHS(HC_SEG_CASE)
 #undef HC_SEG_CASE
     default: break;
@@ -574,18 +582,18 @@ __device__ __forceinline__ void seg_wave(const LaneArgs& a, int wid, const float
 template <int OCC>
 __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
 {
-    // Each wave fills its own copy of the prior pair table (seg_common.hpp
-    // ptab, 4 KB): no workgroup barrier between the kernel's start and a
-    // wave's first loads, so the fill overlaps the wave's descriptor loads
-    // (small batches are one round of waves: every wave's start-up latency is
-    // on the pass's critical path). The region also takes the quad table (10
-    // KB, rows of 256 bytes, each wave's 256-byte aligned: a row's base and
-    // the pattern bits are joined by an OR), which a wide wave whose qualities
-    // fit it writes over the pair table (run_seg_bc): 12.5 KB of LDS per wave
-    // with the match window, 12 waves per CU in 160 KiB.
-    __shared__ __attribute__((aligned(256))) float ptabs[kSegWPB][kPriorLdsLen];
-    static_assert(kPriorLdsLen * 4 % 256 == 0, "every wave's table 256-byte aligned");
-    static_assert(kSegWPB * (kPriorLdsLen * 4 + 5 * 64 * 8) <= 160 * 1024 / 12 * kSegWPB, "12 waves per CU");
+    // The workgroup's prior tables (seg_common.hpp): the pair table with its
+    // pm / px arrays (5 KB) and the quad table of 64 quality rows of 256 bytes
+    // (16 KB, 256-byte aligned: a row's base and the pattern bits share no
+    // bit). All the workgroup's waves fill them and meet at one barrier; a wave
+    // keeps only its match window for itself (5 KB spread, seg_wave). Per-wave
+    // tables (round 4 to 12) left no room for the spread window at 12 waves per
+    // CU; the workgroup's cost 21.5 KB + kSegWPB * 5 KB, and workgroups of four
+    // waves sit three to a CU.
+    __shared__ __attribute__((aligned(256))) float qtab[kQuadLen > 0 ? kQuadLen : 1];
+    __shared__ __attribute__((aligned(16))) float ptab[kPtabLen];
+    constexpr int kWgLds = (kQuadLen + kPtabLen) * 4 + 256 + kSegWPB * kWindowBytes;   // 256: alignment slack
+    static_assert(12 % kSegWPB == 0 && kWgLds * (12 / kSegWPB) <= 160 * 1024, "12 waves per CU");
     const int n_waves = a.n_waves_dev ? __builtin_amdgcn_readfirstlane(*a.n_waves_dev) : a.n_waves;
     const int wib = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
     const int wid = blockIdx.x * kSegWPB + wib;
@@ -599,11 +607,12 @@ __global__ __launch_bounds__(64 * kSegWPB, OCC) void phmm_seg_kernel(LaneArgs a)
         c[kPlanTicket + o] = 0;
         c[kPlanReady + o] = 0;
     }
+    // Every wave of the workgroup takes part in the fill and its barrier, the
+    // ones past the last wave of the launch too; they leave behind it.
+    fill_shared_tabs(ptab, qtab, a.lut, int(threadIdx.x), 64 * kSegWPB);
+    __syncthreads();
     if (wid >= n_waves) return;   // wave-uniform (device-planned parts launch an upper bound)
-    float* ptab = ptabs[wib];
-    fill_ptab(ptab, a.lut, __lane_id());
-    __builtin_amdgcn_wave_barrier();
-    seg_wave(a, wid, ptab);
+    seg_wave(a, wid, ptab, qtab);
 }
 
 // Diagnostics (Seg64Args::timeline): wave w's record.

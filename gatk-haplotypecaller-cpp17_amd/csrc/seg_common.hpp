@@ -9,6 +9,7 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "luts.hpp"
+#include "seg_spread.hpp"
 
 namespace hcphmm {
 namespace seg {
@@ -156,7 +157,7 @@ __device__ __forceinline__ T y_next(T Ml, T Yl, T my, T yy)
 // The fp32 constant-gap path takes its priors from LDS instead of selecting
 // them: two adjacent columns of a row take one of four (prior, prior) pairs that
 // depend only on the row's quality q and the two columns' match bits, so each
-// seg wave keeps ptab[128][4] of float2 (4 KB),
+// workgroup of seg waves keeps ptab[128][4] of float2 (4 KB, fill_shared_tabs),
 //   ptab[q][p] = { p & 2 ? pm[q] : px[q],  p & 1 ? pm[q] : px[q] }
 // (the pair's first column is the higher bit, as in the MSB-first window), and a
 // row reads one ds_read_b64 per two columns. The address is the row's table
@@ -174,22 +175,6 @@ using lds_cfloat2 = const __attribute__((address_space(3))) float2v;
 __device__ __forceinline__ uint32_t lds_addr(const void* p)
 {
     return uint32_t(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
-}
-
-// Each lane writes the rows q = lane and lane + 64 (two 16-byte stores each);
-// wave-private, so the caller needs a wave barrier only.
-__device__ __forceinline__ void fill_ptab(float* __restrict__ ptab, const float* __restrict__ lut, int lane)
-{
-#pragma unroll
-    for (int t = 0; t < kQuals / 64; ++t) {
-        const int q = lane + 64 * t;
-        const float pm = lut[kOffPm + q], px = lut[kOffPx + q];
-        float4* d = reinterpret_cast<float4*>(ptab + q * 8);
-        d[0] = make_float4(px, px, px, pm);   // patterns 00, 01
-        d[1] = make_float4(pm, px, pm, pm);   // patterns 10, 11
-        ptab[kPtabPairs + q] = pm;
-        ptab[kPtabPairs + kQuals + q] = px;
-    }
 }
 
 // Table base of a row: ptab's LDS address + 32 * q.
@@ -244,35 +229,43 @@ constexpr int kPtabAhead = 2;
 // A row covers all 64 banks, so the row does not pick the banks, only the
 // 16-byte column slot does, and the skewed pattern distribution (match bits
 // at p = 0.25) piles the 16 lanes of a ds_read_b128 service group onto a few
-// slots. The physical column is c = pattern ^ (r & 15), which spreads lanes on
+// slots. The physical column is c = pattern ^ (q & 15), which spreads lanes on
 // different rows over all 16 slots (tools/lds_quad_model.py: 19.9 LDS cycles
 // per four columns without, 11.6 with; two ds_read_b64 of 128-byte rows took
-// 12.5). The XOR is applied to the row's two window words, once per row, with
-// the nibble replicated eight times.
-// 128 such rows do not fit a wave's share of the LDS (12 waves per CU in
-// 160 KiB: 13 653 bytes, 2 560 of them the match window), so the table covers
-// kQuadRows consecutive qualities from the lowest of the wave's own reads
-// (quad_scan); a wave whose reads span more keeps the pair table. The quad
-// table lies over the pair table and the pm/px arrays (one region, fill_ptab
-// first for every wave, fill_qtab over it for a quad wave); the region is
-// 256-byte aligned, so a row's base | (pattern bits << 4) is an address.
-// HC_PTAB_NO_QUAD (EXTRA_DEV_FLAGS, A/B builds): every width keeps the pair table.
+// 12.5).
+// The table is the workgroup's, kQuadRows = 64 rows indexed by the absolute
+// quality, filled once by all its waves (fill_shared_tabs): the row of quality
+// byte q is q & 63 and the table holds the bytes kQuadQ0 = 33 .. 96, Phred 0 ..
+// 63 of a SAM quality string. A wave takes it when every quality of its reads
+// is one of those (quad_scan); the others keep the pair table, the
+// workgroup's too. What a wave keeps for
+// itself is its match window, and a quad wave keeps it SPREAD (seg_spread.hpp):
+// one byte per group of four columns holding pattern << 4, so a group's table
+// address is base2 ^ byte, one ds_read_u8 (no VALU slot) and one v_xor_b32,
+// where the packed window took a shift and a v_and_or_b32 (3 slots). base2 is
+// the row's base with its swizzle nibble already at bits 7:4 (a row is
+// 256-byte aligned, so (base | n << 4) ^ (p << 4) == base | ((p ^ n) << 4)):
+// no per-row XOR of the window and no replicated nibble.
+// HC_PTAB_NO_QUAD (EXTRA_DEV_FLAGS, A/B builds): every width keeps the pair
+// table and the packed window; the byte form is compiled out.
 // HC_QUAD_NO_SWIZZLE (likewise): the physical column is the pattern.
 #ifdef HC_QUAD_NO_SWIZZLE
 constexpr bool kQuadSwizzle = false;
 #else
 constexpr bool kQuadSwizzle = true;
 #endif
-constexpr int kQuadRows = 40;                          // Phred 2..41 spans exactly 40
+constexpr int kQuadRows = 64;
+constexpr int kQuadQ0 = 33;   // the lowest quality byte the table holds (Phred 0)
 constexpr int kQuadRowBytes = 256;
-constexpr int kQuadLen = kQuadRows * kQuadRowBytes / 4;   // floats of the quad table
 // Widths whose quad form fits the register budget (168 VGPRs, no scratch).
 #ifdef HC_PTAB_NO_QUAD
 constexpr int kQuadMinWidth = 1 << 30, kQuadMaxWidth = 0;
-constexpr int kPriorLdsLen = kPtabLen;
+constexpr int kQuadLen = 0;
+constexpr int kWindowBytes = 5 * 64 * 8;
 #else
 constexpr int kQuadMinWidth = kPtabMinWidth, kQuadMaxWidth = 64;
-constexpr int kPriorLdsLen = kQuadLen > kPtabLen ? kQuadLen : kPtabLen;
+constexpr int kQuadLen = kQuadRows * kQuadRowBytes / 4;   // floats of the quad table
+constexpr int kWindowBytes = kSpreadWaveBytes;            // a wave's window, packed (2 560) or spread
 #endif
 template <typename T, int BC>
 constexpr bool quad_width()
@@ -294,87 +287,95 @@ __device__ __forceinline__ int wave_min(int v)
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-// Rows r = 4t + lane / 16 (t = 0..9), pattern p = lane & 15: one 16-byte store
-// per row. Qualities past 127 (a window that starts above 88) are rows no read
-// selects. pm and px come from the arrays behind the pair table (fill_ptab),
-// which this table overwrites: every lane reads all of its own before the
-// wave's first store.
-__device__ __forceinline__ void fill_qtab(float* tab, int lane, int qmin)
+// The workgroup's tables, filled by all its nt threads (thread t): the pair
+// table with its pm / px arrays (two 16-byte stores per quality) and the quad
+// table (one 16-byte store per row and pattern). The caller's __syncthreads()
+// follows.
+__device__ __forceinline__ void fill_ptab(float* __restrict__ ptab, const float* __restrict__ lut, int t, int nt)
 {
-    const int p = lane & 15;
-    float pmr[kQuadRows / 4], pxr[kQuadRows / 4];
-#pragma unroll
-    for (int t = 0; t < kQuadRows / 4; ++t) {
-        const int q = min(qmin + 4 * t + (lane >> 4), kQuals - 1);
-        pmr[t] = lds_pm(tab, q);
-        pxr[t] = lds_px(tab, q);
+    for (int q = t; q < kQuals; q += nt) {
+        const float pm = lut[kOffPm + q], px = lut[kOffPx + q];
+        float4* d = reinterpret_cast<float4*>(ptab + q * 8);
+        d[0] = make_float4(px, px, px, pm);   // patterns 00, 01
+        d[1] = make_float4(pm, px, pm, pm);   // patterns 10, 11
+        ptab[kPtabPairs + q] = pm;
+        ptab[kPtabPairs + kQuals + q] = px;
     }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int t = 0; t < kQuadRows / 4; ++t) {
-        const int r = 4 * t + (lane >> 4);
-        const float pm = pmr[t], px = pxr[t];
+}
+__device__ __forceinline__ void fill_qtab(float* __restrict__ qtab, const float* __restrict__ lut, int t, int nt)
+{
+    for (int e = t; e < kQuadLen / 4; e += nt) {
+        const int r = e >> 4, p = e & 15;
+        const int q = kQuadQ0 + ((r - kQuadQ0) & (kQuadRows - 1));   // the byte of the table's range with q & 63 == r
+        const float pm = lut[kOffPm + q], px = lut[kOffPx + q];
         const int c = kQuadSwizzle ? p ^ (r & 15) : p;
-        *reinterpret_cast<float4*>(tab + r * (kQuadRowBytes / 4) + c * 4) =
+        *reinterpret_cast<float4*>(qtab + r * (kQuadRowBytes / 4) + c * 4) =
             make_float4((p & 8) ? pm : px, (p & 4) ? pm : px, (p & 2) ? pm : px, (p & 1) ? pm : px);
     }
 }
-
-// Table row and swizzle of a read row with quality q: r = q - qmin clamped
-// into the table (a prefetched row outside every read can carry any quality;
-// no result depends on what it selects), the row's base address and the
-// swizzle nibble replicated over a window word.
-__device__ __forceinline__ void quad_row(uint32_t tab_lds, uint32_t qmin, uint32_t w, uint32_t& base, uint32_t& rep)
+__device__ __forceinline__ void fill_shared_tabs(float* __restrict__ ptab, float* __restrict__ qtab,
+                                                 const float* __restrict__ lut, int t, int nt)
 {
-    const uint32_t r = min(uint32_t(row_q(w)) - qmin, uint32_t(kQuadRows - 1));
-    base = tab_lds + r * kQuadRowBytes;
-    const uint32_t n6 = __umul24(r & 15u, 0x111111u);   // six copies, full rate
-    rep = kQuadSwizzle ? n6 | (n6 << 8) : 0u;
+    fill_ptab(ptab, lut, t, nt);
+    fill_qtab(qtab, lut, t, nt);
 }
 
-// A row's table base (and, QUAD, its swizzle) from its row word.
+// base2 of a read row with quality byte q: the table row q & 63 (a prefetched row
+// outside every read can carry any quality; the mask keeps its address inside
+// the table and no result depends on what it selects) with the swizzle nibble
+// q & 15 at bits 7:4.
+__device__ __forceinline__ uint32_t quad_base2(uint32_t qtab_lds, uint32_t w)
+{
+    return qtab_lds + (((w & 63u) << 8) | (kQuadSwizzle ? (w & 15u) << 4 : 0u));
+}
+
+// A row's table base from its row word (QUAD: base2 of the quad table).
 template <bool QUAD>
-__device__ __forceinline__ void tab_row(uint32_t tab_lds, uint32_t qmin, uint32_t w, uint32_t& base, uint32_t& rep)
+__device__ __forceinline__ uint32_t tab_row(uint32_t tab_lds, uint32_t w)
 {
     if constexpr (QUAD)
-        quad_row(tab_lds, qmin, w, base, rep);
+        return quad_base2(tab_lds, w);
     else
-        base = ptab_row(tab_lds, w);
+        return ptab_row(tab_lds, w);
 }
 
-// The priors of column group G (block columns 4G .. 4G+3) of a row: the four
-// (swizzled) window bits at bits 7:4 of the row's 256-byte-aligned base. The
-// last group of a width that is no multiple of 4 takes its low two bits from
-// the window's next columns; an entry's .x and .y do not depend on them.
+// The byte of column group G (block columns 4G .. 4G+3) of the lane's spread
+// window: slot is the LDS address of the row's (read code, lane). The last
+// group of a width that is no multiple of 4 takes its low two bits from the
+// window's next columns; an entry's .x and .y do not depend on them.
+using lds_cbyte = const __attribute__((address_space(3))) uint8_t;
+template <int G>
+__device__ __forceinline__ uint32_t win_byte(uint32_t slot)
+{
+    return *reinterpret_cast<lds_cbyte*>(slot + spread_group_off(G));
+}
+// The priors of a group from its byte: the pattern at bits 7:4 meets the row's
+// swizzle nibble there.
 typedef float float4v __attribute__((ext_vector_type(4)));
 using lds_cfloat4 = const __attribute__((address_space(3))) float4v;
-template <int G>
-__device__ __forceinline__ float4 quad_read(uint32_t base, const uint2& m)
+__device__ __forceinline__ float4 quad_read(uint32_t base2, uint32_t byte)
 {
-    constexpr int sh = 28 - 4 * (G & 7);
-    const uint32_t w = (G >> 3) ? m.y : m.x;
-    uint32_t bits;
-    if constexpr (sh >= 4)
-        bits = w >> (sh - 4);
-    else
-        bits = w << (4 - sh);
-    const float4v v = *reinterpret_cast<lds_cfloat4*>(base | (bits & 0xf0u));
+    const float4v v = *reinterpret_cast<lds_cfloat4*>(base2 ^ byte);
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
 // What one table read gives and a row keeps a ring of: entry E of a row is a
 // pair of columns' priors (pair table) or a group of four (quad table).
 template <bool QUAD> using TabEnt = std::conditional_t<QUAD, float4, float2>;
-template <bool QUAD, int E>
-__device__ __forceinline__ TabEnt<QUAD> tab_ent(uint32_t base, const uint2& mrow)
-{
-    if constexpr (QUAD)
-        return quad_read<E>(base, mrow);
-    else
-        return ptab_pair<E>(base, mrow);
-}
 __device__ __forceinline__ float ent_el(const float2& v, int e) { return e ? v.y : v.x; }
 __device__ __forceinline__ float ent_el(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+
+// What a table row reads its entries with. Pair table: the row's base and its
+// packed window. Quad table: base2, the lane's window slot and the byte of the
+// next group to read, requested one group before its address is formed.
+template <bool QUAD> struct TabRow;
+template <> struct TabRow<false> {
+    uint32_t base;
+    uint2 m;
+};
+template <> struct TabRow<true> {
+    uint32_t base, slot, byte;
+};
 
 // Column J of one row, fp32 EQ path with table priors: `cell`'s EQ arithmetic
 // in the same order. An entry holds the priors of N columns (pair table 2,
@@ -387,12 +388,14 @@ __device__ __forceinline__ float ent_el(const float4& v, int e) { return e == 0 
 // lets VALU work through and keeps the LDS reads where they are (hoisted to
 // the row's start they take an entry's registers each, sunk to their use the
 // wave waits on every one).
-// QUAD: mrow is the swizzled window. A width with BC % 4 == 2 ends in a half
-// group: its read takes 16 bytes and the cells use .x and .y.
+// QUAD: with the read of group e + 2 goes the request of group e + 3's byte,
+// so a byte is in flight for a whole group before its address is formed. A
+// width with BC % 4 == 2 ends in a half group: its read takes 16 bytes and the
+// cells use .x and .y.
 template <int BC, int J, bool SUM, int D, bool QUAD>
 __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float M, float& Ml, float& Yl,
-                                         TabEnt<QUAD> (&pr)[D], uint32_t base, const uint2& mrow,
-                                         const RowConst<float>& k, float& sumM, float& sumX)
+                                         TabEnt<QUAD> (&pr)[D], TabRow<QUAD>& tr, const RowConst<float>& k,
+                                         float& sumM, float& sumX)
 {
     constexpr int N = QUAD ? 4 : 2;           // columns per entry
     constexpr int NE = (BC + N - 1) / N;      // entries of a row
@@ -402,7 +405,12 @@ __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float 
         if constexpr (J % N == N - 2 && J / N + D < NE) {
             constexpr int kNoDs = 0x2 | 0x4 | 0x10 | 0x20 | 0x40;   // VALU, SALU and VMEM may cross; DS may not
             __builtin_amdgcn_sched_barrier(0);
-            pr[(J / N + D) % D] = tab_ent<QUAD, J / N + D>(base, mrow);
+            if constexpr (QUAD) {
+                pr[(J / N + D) % D] = quad_read(tr.base, tr.byte);
+                if constexpr (J / N + D + 1 < NE) tr.byte = win_byte<J / N + D + 1>(tr.slot);
+            } else {
+                pr[(J / N + D) % D] = ptab_pair<J / N + D>(tr.base, tr.m);
+            }
             __builtin_amdgcn_sched_barrier(kNoDs);
         }
         const float Xc = X[J];
@@ -416,7 +424,7 @@ __device__ __forceinline__ void cell_tab(float (&Tt)[BC], float (&X)[BC], float 
         X[J] = Mx + Xc * k.xx;
         Ml = Mx;
         Yl = Y;
-        cell_tab<BC, J + 1, SUM, D, QUAD>(Tt, X, Mn, Ml, Yl, pr, base, mrow, k, sumM, sumX);
+        cell_tab<BC, J + 1, SUM, D, QUAD>(Tt, X, Mn, Ml, Yl, pr, tr, k, sumM, sumX);
     }
 }
 
@@ -623,7 +631,11 @@ __device__ __forceinline__ void load_slut(T* __restrict__ slut, const T* __restr
 // the reference's sums, with no per-column mask.
 // A lane's match window: columns c0+1 .. c0+64 of the hap's match table
 // (rows of 32 bits, MSB first, kHapLead zero rows before), for each of the 5
-// read codes, into its LDS slots mt[code * 64 + lane].
+// read codes, into its LDS slots mt[code * 64 + lane]. SPREAD (quad waves):
+// the same 64 columns as 16 bytes, a group of four columns each
+// (seg_spread.hpp), in the same region; padding columns left of column 1 and
+// columns past the hap are zero bits in both forms.
+template <bool SPREAD = false>
 __device__ __forceinline__ void fill_window(uint2* __restrict__ mt, int lane, const LaneCtx& cx, int c0)
 {
     const int H = cx.H;
@@ -635,20 +647,29 @@ __device__ __forceinline__ void fill_window(uint2* __restrict__ mt, int lane, co
         const uint32_t h0 = hap_word(cx, i0 * 5 + c), h1 = hap_word(cx, i1 * 5 + c), h2 = hap_word(cx, i2 * 5 + c);
         const uint64_t x01 = (uint64_t(h0) << 32) | h1;
         const uint64_t x12 = (uint64_t(h1) << 32) | h2;
-        mt[c * 64 + lane] = make_uint2(uint32_t((x01 << r) >> 32), uint32_t((x12 << r) >> 32));
+        const uint32_t m0 = uint32_t((x01 << r) >> 32), m1 = uint32_t((x12 << r) >> 32);
+        if constexpr (SPREAD) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(mt) + spread_slot_off(c, lane) / 4;
+            d[spread_group_off(0) / 4] = spread_nibbles(m0 >> 16);
+            d[spread_group_off(4) / 4] = spread_nibbles(m0 & 0xffffu);
+            d[spread_group_off(8) / 4] = spread_nibbles(m1 >> 16);
+            d[spread_group_off(12) / 4] = spread_nibbles(m1 & 0xffffu);
+        } else {
+            mt[c * 64 + lane] = make_uint2(m0, m1);
+        }
     }
 }
 
 // slut: the wave's prior tables in LDS. fp64: [ph2pr | pm | px | gapm]
 // (load_slut); fp32: the pair table ptab (fill_ptab), which the constant-gap
 // EQ path of the wide blocks (TAB) reads two columns at a time (cell_tab).
-// QUAD (table widths of the fp32 EQ path only): slut holds the quad table of
-// the qualities qmin .. qmin + kQuadRows - 1 (fill_qtab), which cover every
-// row of the wave's reads.
+// QUAD (table widths of the fp32 EQ path only): slut is the workgroup's quad
+// table, whose rows cover every quality of the wave's reads, and the window
+// is kept spread.
 template <typename T, int BC, bool CG, bool EQ, bool QUAD = false>
 __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __restrict__ slut, const SegSteps& st,
                                         int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
-                                        uint2* __restrict__ mt, uint32_t w1, uint32_t qmin = 0)
+                                        uint2* __restrict__ mt, uint32_t w1)
 {
     constexpr int PD = seg_prefetch<T, BC>();
     constexpr bool TAB = std::is_same<T, float>::value && CG && EQ && BC >= kPtabMinWidth;
@@ -663,7 +684,7 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     // spilled once the paths' prologues differ. A text that differs per path
     // ends that at the first instruction.
     asm volatile("; run_seg CG=%1 QUAD=%2" : "+v"(c0) : "n"(int(CG)), "n"(int(QUAD)));
-    fill_window(mt, lane, cx, c0);
+    fill_window<QUAD>(mt, lane, cx, c0);
     T Tt[BC], X[BC];
 #pragma unroll
     for (int j = 0; j < BC; ++j) {
@@ -687,20 +708,40 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     for (int P = 0; P < PD; ++P) wq[P] = row_word(cx, min(max(P + 2 - s, 1), R) - 1);
     RowConst<T> k;
     row_const<T>(lut, wc, row_word(cx, min(2, R) - 1), k);
-    uint2 mrow = mt[k.rc * 64 + lane];
-    // TAB: ptab's LDS address, the coming row's table base and its first
+    uint2 mrow{};
+    if constexpr (!TAB) mrow = mt[k.rc * 64 + lane];
+    // TAB: the table's LDS address, the coming row's table base and its first
     // entry (pair, or QUAD group of four), read at the end of the step before
     // (here: row 1's).
-    // QUAD: mrow is the swizzled window (the cells of a table row do not
-    // consume it).
-    uint32_t ptab_lds = 0, base = 0;
+    // QUAD: the lane's slot of the spread window for the row's read code and
+    // the byte of the row's second group ride along; mrow is unused.
+    uint32_t tab_lds = 0, win_lds = 0;
+    TabRow<TAB && QUAD> tr{};
     TabEnt<QUAD> pr0{};
+    // TAB: what row w's cells start with. w's last uses are the window's slot
+    // and the table base, and `after` (the index of the row word loaded next)
+    // is ordered behind them, so that word can land in w's register.
+    auto row_reads = [&](uint32_t w, int& after) {
+        tr.base = tab_row<QUAD>(tab_lds, w);
+        if constexpr (QUAD) {
+            // (from the lane id each row, as the packed window's slot is: a
+            // register held across the step loop is one the widest block lacks)
+            tr.slot = win_lds + spread_slot_off(row_rc(w), lane);
+            asm volatile("" : "+v"(after) : "v"(tr.slot), "v"(tr.base));
+            pr0 = quad_read(tr.base, win_byte<0>(tr.slot));
+            tr.byte = win_byte<1>(tr.slot);
+        } else {
+            const int mo = row_rc(w) * 64 + lane;
+            asm volatile("" : "+v"(after) : "v"(mo), "v"(tr.base));
+            tr.m = mt[mo];
+            pr0 = ptab_pair<0>(tr.base, tr.m);
+        }
+    };
     if constexpr (TAB) {
-        ptab_lds = lds_addr(slut);
-        uint32_t rep = 0;
-        tab_row<QUAD>(ptab_lds, qmin, wc, base, rep);
-        if constexpr (QUAD) mrow = make_uint2(mrow.x ^ rep, mrow.y ^ rep);
-        pr0 = tab_ent<QUAD, 0>(base, mrow);
+        tab_lds = lds_addr(slut);
+        if constexpr (QUAD) win_lds = lds_addr(mt);
+        int none = 0;
+        row_reads(wc, none);
     }
     // A pair's last block (and any lane past it) hands zeros to the lane on its
     // right, so a group's first lane needs no select: it receives Y = 0 entering
@@ -769,13 +810,17 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
             if constexpr (TAB) {
                 constexpr int D = kPtabAhead;
                 constexpr int NE = QUAD ? (BC + 3) / 4 : NP;   // table entries of a row
+                static_assert(D == 2 && NE > D, "the ring holds two entries; a table row has more");
                 TabEnt<QUAD> pr[D];
                 pr[0] = pr0;
-                for_phases<1, (D < NE ? D : NE)>([&](auto p) {
-                    pr[decltype(p)::value] = tab_ent<QUAD, decltype(p)::value>(base, mrow);
-                });
+                if constexpr (QUAD) {
+                    pr[1] = quad_read(tr.base, tr.byte);
+                    tr.byte = win_byte<2>(tr.slot);
+                } else {
+                    pr[1] = ptab_pair<1>(tr.base, tr.m);
+                }
                 const float M0 = Tdiag * pr0.x;
-                cell_tab<BC, 0, SUM, D, QUAD>(Tt, X, M0, Ml, Yl, pr, base, mrow, k, sumM, sumX);
+                cell_tab<BC, 0, SUM, D, QUAD>(Tt, X, M0, Ml, Yl, pr, tr, k, sumM, sumX);
             } else {
                 const T M0 = Tdiag * prior_next(mrow.x, k.pm, k.px);   // bit 31 of mrow.x first
                 cell<T, BC, 0, BC, SUM, EQ>(Tt, X, M0, Ml, Yl, mrow.x, mrow.y, k.pm, k.px, k, 0, sumM, sumX);
@@ -786,18 +831,7 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
         if constexpr (TAB) {
             // Unconditional, as below. wn's last uses are the window's slot and
             // the table base, so the word loaded now can land in wn's register.
-            const int mo = row_rc(wn) * 64 + lane;
-            uint32_t rep = 0;
-            tab_row<QUAD>(ptab_lds, qmin, wn, base, rep);
-            if constexpr (QUAD) {
-                asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base), "v"(rep));
-                const uint2 m = mt[mo];
-                mrow = make_uint2(m.x ^ rep, m.y ^ rep);
-            } else {
-                asm volatile("" : "+v"(ridx) : "v"(mo), "v"(base));
-                mrow = mt[mo];
-            }
-            pr0 = tab_ent<QUAD, 0>(base, mrow);
+            row_reads(wn, ridx);
             wq[P] = row_word(cx, ridx);
         } else if constexpr (CG) {
             // Unconditional (no register moves for a conditional update): a
@@ -833,15 +867,15 @@ __device__ __forceinline__ void run_seg(const T* __restrict__ lut, const T* __re
     }
 }
 
-// Lowest and highest quality of the rows of the wave's reads. Lane s of a
-// pair's nb lanes takes the rows 4s .. 4s + 3, 4(s + nb) .. of its read, eight
-// 16-byte loads in flight (a load past the read's end repeats the first; the
-// rows behind a read's last are there to load, part_setup.hpp row_pad_words,
-// and are left out of the result).
+// Whether every row of the wave's reads has a quality the quad table holds
+// (kQuadQ0 .. kQuadQ0 + 63: bit 6 of (q - kQuadQ0) mod 128 clear). Lane s of a pair's nb lanes takes the rows 4s .. 4s + 3,
+// 4(s + nb) .. of its read, eight 16-byte loads in flight (a load past the
+// read's end repeats the first; the rows behind a read's last are there to
+// load, part_setup.hpp row_pad_words, and are left out of the result).
 typedef uint32_t rows4 __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ void quad_scan(const LaneCtx& cx, int s, int nb, int& qmin, int& qmax)
+__device__ __forceinline__ bool quad_scan(const LaneCtx& cx, int s, int nb)
 {
-    int lo = kQuals - 1, hi = 0;
+    uint32_t high = 0;   // the OR of the rows' words less kQuadQ0: the low 7 bits are (q - kQuadQ0) mod 128
     const int last = cx.R - 1;
     constexpr int NL = 8;   // loads in flight
     for (int i = 4 * s; i <= last; i += 4 * NL * nb) {
@@ -856,35 +890,27 @@ __device__ __forceinline__ void quad_scan(const LaneCtx& cx, int s, int nb, int&
 #pragma unroll
         for (int t = 0; t < NL; ++t)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int q = at[t] + j <= last ? row_q(w[t][j]) : lo;
-                lo = min(lo, q);
-                hi = max(hi, q);
-            }
+            for (int j = 0; j < 4; ++j)
+                if (at[t] + j <= last) high |= w[t][j] - uint32_t(kQuadQ0);
     }
-    qmin = wave_min(lo);
-    qmax = wave_max(hi);
+    static_assert(kQuals == 2 * kQuadRows, "one bit tells the table's half of the qualities from the other");
+    return __builtin_amdgcn_ballot_w64((high & uint32_t(kQuadRows)) != 0) == 0;
 }
 
 // Two compiled paths per width: EQ (the reference's constant 'I'/'I'/'+' gap
-// qualities) and the generic per-row path (any gap qualities).
+// qualities) and the generic per-row path (any gap qualities); the table
+// widths of the fp32 EQ path a third, on the quad table qtab, for the waves
+// whose qualities it holds.
 template <typename T, int BC>
 __device__ __forceinline__ void run_seg_bc(const T* __restrict__ lut, const T* __restrict__ slut, const SegSteps& st,
                                            int lane, int s, const LaneCtx& cx, T T0, T& sumM, T& sumX,
-                                           uint2* __restrict__ mt, bool wave_eq, uint32_t w1)
+                                           uint2* __restrict__ mt, bool wave_eq, uint32_t w1,
+                                           const T* __restrict__ qtab = nullptr)
 {
     if constexpr (quad_width<T, BC>()) {
-        // slut is the wave's prior region, writable: the quad table goes over
-        // the pair table when the wave's qualities fit its rows.
-        if (wave_eq) {
-            int qmin, qmax;
-            quad_scan(cx, s, (cx.H + BC - 1) / BC, qmin, qmax);
-            if (qmax - qmin < kQuadRows) {
-                fill_qtab(const_cast<T*>(slut), lane, qmin);
-                __builtin_amdgcn_wave_barrier();
-                run_seg<T, BC, true, true, true>(lut, slut, st, lane, s, cx, T0, sumM, sumX, mt, w1, uint32_t(qmin));
-                return;
-            }
+        if (wave_eq && quad_scan(cx, s, (cx.H + BC - 1) / BC)) {
+            run_seg<T, BC, true, true, true>(lut, qtab, st, lane, s, cx, T0, sumM, sumX, mt, w1);
+            return;
         }
     }
     if (wave_eq)

@@ -29,7 +29,10 @@ ds_read_b64 of the pair, reported as "prior table (address)" and "prior table
 and reads 16 bytes at it (ds_read_b128, the priors of all four): a loop with
 such reads is marked "quad". (Round 11's quad form read twice at the address,
 ds_read_b64 with and without a DS immediate offset: both count as table reads,
-and such a loop is marked "quad" as well.)"""
+and such a loop is marked "quad" as well.) The byte form (seg_spread.hpp) reads
+a group's pattern byte from the spread window (ds_read_u8, a table read: no VALU
+slot) and forms the address with one v_xor_b32 of that byte and the row's base
+(full rate, 1 slot, "prior table (address)"): such a loop is marked "byte"."""
 import collections
 import json
 import re
@@ -59,9 +62,19 @@ def table_roles(ins):
     address (the address stays a table address until a VALU instruction
     overwrites its register: the two-read quad form read twice at it)."""
     addr, read = set(), set()
-    shift_of, addr_regs = {}, set()
+    shift_of, addr_regs, byte_regs = {}, set(), set()
     for i, (op, t) in enumerate(ins):
         a = operands(t)
+        if op == "ds_read_u8":
+            read.add(i)
+            addr_regs.discard(a[0])
+            byte_regs.add(a[0])
+            continue
+        if op == "v_xor_b32" and (a[1] in byte_regs or a[2] in byte_regs):
+            addr.add(i)
+            byte_regs.discard(a[0])
+            addr_regs.add(a[0])
+            continue
         if op == "v_and_or_b32":
             addr.add(i)
             if a[1] in shift_of:
@@ -73,6 +86,7 @@ def table_roles(ins):
         if a and op.startswith("v_"):
             shift_of.pop(a[0], None)
             addr_regs.discard(a[0])
+            byte_regs.discard(a[0])
             if op in ("v_lshrrev_b32", "v_lshlrev_b32"):
                 shift_of[a[0]] = i
     return addr, read
@@ -185,11 +199,13 @@ def main():
             if writes_vcc(op, t):
                 carry = op == "v_add_co_u32"
         quad = any(op == "ds_read_b128" or "offset:" in t for i, (op, t) in enumerate(ins) if i in tab_read)
-        rows.append(dict(kernel=lines[start].split(":")[0], loop=hdr, fp64=fp64, bc=bc, eq=eq, quad=quad, row_sums=sums, steps_per_iteration=steps,
+        byte = any(op == "ds_read_u8" for i, (op, t) in enumerate(ins) if i in tab_read)
+        rows.append(dict(kernel=lines[start].split(":")[0], loop=hdr, fp64=fp64, bc=bc, eq=eq, quad=quad, byte=byte, row_sums=sums, steps_per_iteration=steps,
                          s_nop_per_step=round(c["s_nop"] / steps, 2),
                          select_ops_per_step={k: round(c[k] / steps, 2) for k in
                                               ("v_add_co_u32", "v_cndmask_b32", "v_bfe_i32", "v_bitop3_b32")},
-                         table_ops_per_step={k: round(c[k] / steps, 2) for k in ("v_and_or_b32", "ds_read_b64", "ds_read_b128")},
+                         table_ops_per_step={k: round(c[k] / steps, 2) for k in ("v_and_or_b32", "ds_read_b64", "ds_read_b128", "ds_read_u8")},
+                         table_address_xor_per_step=round(sum(1 for i in tab_addr if ins[i][0] == "v_xor_b32") / steps, 2),
                          cndmask_e64_per_step=round(sum(1 for op, t in ins if op == "v_cndmask_b32"
                                                         and t.split()[0].endswith("_e64")) / steps, 2),
                          arith_per_step=arith / steps,

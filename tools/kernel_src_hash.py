@@ -26,7 +26,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gatk-haplotypecaller-cpp17_amd")
 SRC = os.path.join(PKG, "csrc")
-FILES = ["lane_kernel.hip", "seg_common.hpp", "kernels.hpp", "kernels.hip", "pack_kernels.hip", "luts.hpp",
+FILES = ["lane_kernel.hip", "seg_common.hpp", "seg_spread.hpp", "kernels.hpp", "kernels.hip", "pack_kernels.hip", "luts.hpp",
          "device_common.hpp"]
 
 

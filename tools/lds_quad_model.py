@@ -19,11 +19,23 @@ match bit set with probability p (0.25: a row of a read against a random hap).
     b128 table   a = 256 r + 16 c, one 16-byte read per four columns, plain or
                  with c = bits ^ (r & 15)                   (fill_qtab, quad_row)
 
-    python tools/lds_quad_model.py [--json OUT] [--json128 OUT128]
+    shared table a = 256 (q & 63) + 16 (bits ^ (q & 15)), the workgroup's 64 rows by
+                 absolute quality                           (fill_shared_tabs, quad_base2)
+    window byte  a = 1024 code + 256 (g / 4) + 4 lane + g % 4, the spread window's
+                 ds_read_u8 of group g                      (seg_spread.hpp)
+
+    python tools/lds_quad_model.py [--json OUT] [--json128 OUT128] [--json-byte OUTB]
 
 --json writes the ds_read_b64 layouts (per read), --json128 the comparison per
 four columns: two ds_read_b64 of the swizzled quad table against one
-ds_read_b128, with the spread of each over SEEDS further seeds.
+ds_read_b128, with the spread of each over SEEDS further seeds. --json-byte
+writes the byte form's: the ds_read_b128 of the shared 64-row table and the
+ds_read_u8 of the spread window, one of each per four columns.
+
+A read of four bytes or fewer is served in one group of all 64 lanes, and lanes
+in the same dword share it: the byte read is conflict-free by layout, since the
+lanes of one group's read sit in 64 consecutive dwords whatever their codes
+(byte_read_cycles checks it for every group over random codes).
 """
 import json
 import sys
@@ -37,6 +49,7 @@ B128_GROUPS = [
     list(range(32, 36)) + list(range(44, 48)) + list(range(52, 60)),
     list(range(36, 44)) + list(range(48, 52)) + list(range(60, 64)),
 ]
+B32_GROUPS = [list(range(64))]
 SEEDS = 8   # further seeds for the seed-to-seed spread (fewer draws each)
 
 
@@ -71,6 +84,27 @@ def per_four_columns(r, pat4):
     return (2 * cycles(128 * r + 8 * (pat4 ^ ((r >> 1) & 15))),
             cycles(256 * r + 16 * (pat4 ^ (r & 15)), B128_GROUPS, 16),
             cycles(256 * r + 16 * pat4, B128_GROUPS, 16))
+
+
+def shared_table_addr(q, pat4):
+    """The workgroup's quad table: row q & 63, column pattern ^ (q & 15)."""
+    return 256 * (q & 63) + 16 * (pat4 ^ (q & 15))
+
+
+def window_byte_addr(code, g, lane=None):
+    """Byte address of group g of (code, lane) in a wave's spread window."""
+    lane = np.arange(64) if lane is None else lane
+    return 1024 * code + 256 * (g // 4) + 4 * lane + g % 4
+
+
+def byte_read_cycles(rng, n=2000):
+    """LDS cycles of the ds_read_u8 of each of the 16 groups, lanes on random read
+    codes: [1.0] * 16 when the layout is conflict-free."""
+    out = []
+    for g in range(16):
+        a = window_byte_addr(rng.integers(0, 5, (n, 64)), g)
+        out.append(float(cycles(a // 4 * 4, B32_GROUPS, 4)))
+    return out
 
 
 def main():
@@ -108,7 +142,18 @@ def main():
             x["lds_cycles_per_read"] = round(float(main4[0]) / 2, 2)
         rows128.append(x)
         print(json.dumps(x))
-    for path, rr in ((out, rows), (out128, rows128)):
+    outb = sys.argv[sys.argv.index("--json-byte") + 1] if "--json-byte" in sys.argv else None
+    shared = cycles(shared_table_addr(q, pat4), B128_GROUPS, 16)
+    bytes_ = byte_read_cycles(np.random.default_rng(11))
+    rowsb = [dict(layout="ds_read_b128, 64 rows of 256 bytes by q & 63, column ^ (q & 15)",
+                  lds_cycles_per_four_columns=round(float(shared), 2), conflict_free=4,
+                  lanes="independent", q=[qlo, qhi], p_match=p, draws=n),
+             dict(layout="ds_read_u8, spread window [code][g / 4][lane][g % 4]",
+                  lds_cycles_per_four_columns=round(max(bytes_), 2), conflict_free=1, groups=16,
+                  lanes="random read codes", draws=2000)]
+    for x in rowsb:
+        print(json.dumps(x))
+    for path, rr in ((out, rows), (out128, rows128), (outb, rowsb)):
         if path:
             with open(path, "w") as f:
                 for x in rr:
