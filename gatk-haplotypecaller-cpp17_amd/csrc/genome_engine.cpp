@@ -30,7 +30,9 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hc_bam.h"
 #include "../../include/hc_genome.h"
+#include "genome_engine.hpp"
 #include "genome_kernels.hpp"
 #include "genome_sort_kernels.hpp"
 #include "pool.hpp"
@@ -41,27 +43,11 @@
 using namespace hcgenome;
 using namespace stage_host;
 
-struct hc_genome_result {
-    hc_sam_result* sam = nullptr;
-    std::vector<hc_call_result*> batches;
-    int64_t region = 0, padding = 0;
-    std::vector<std::string> names;          // per contig
-    std::vector<int64_t> ref_len, win_off;   // per contig; n_contigs + 1: a contig's first window
-    std::vector<int32_t> n_records;          // per contig: the records resolved to it
-    std::vector<int32_t> contig_of;          // per record
-    std::vector<int32_t> win_contig;         // per window
-    std::vector<int64_t> win_first;          // n_windows + 1: a window's first pick
-    std::vector<int32_t> picked;             // record indices
-    std::vector<int32_t> status, asm_status, kmer_size, n_haps;   // per window
-    std::vector<hc_gt_call_site> sites;      // `region` renumbered to the genome-wide window
-    std::vector<std::vector<int32_t>> reads; // per window: the surviving reads, record indices
-    std::string vcf;
-    ~hc_genome_result()
-    {
-        for (hc_call_result* b : batches) (void)hc_call_result_free(b);
-        (void)hc_sam_result_free(sam);
-    }
-};
+hc_genome_result::~hc_genome_result()
+{
+    for (hc_call_result* b : batches) (void)hc_call_result_free(b);
+    (void)hc_sam_result_free(sam);
+}
 
 namespace {
 
@@ -98,6 +84,7 @@ const char* defect_text(int d)
         case HC_SAM_DEFECT_CIGAR_LENGTH: return "the CIGAR's read length differs from seq_len";
         case HC_SAM_DEFECT_QUAL_LENGTH: return "qual_len differs from seq_len";
         case HC_SAM_DEFECT_TOO_LONG: return "seq_len above HC_PHMM_MAX_READ_LEN";
+        case HC_SAM_DEFECT_QUAL_RANGE: return "a quality above 93";
         default: return "an unknown defect";
     }
 }
@@ -120,14 +107,6 @@ Bounds bounds_of(const hc_genome_result& r, int64_t w)
     b.ref_len = int32_t(std::min(b.padded_end, r.ref_len[c]) - b.padded_begin);   // substr cuts at the contig's end
     return b;
 }
-
-// The table as the device reads it, in one block: [ref_len | off | win_off | name_off | slots | pool].
-struct Table {
-    std::vector<char> blob;
-    size_t o_len = 0, o_off = 0, o_win = 0, o_name = 0, o_slots = 0, o_pool = 0;
-    uint32_t n_slots = 0;
-    std::vector<int64_t> off;   // n_contigs + 1
-};
 
 // Names into the pool and the hash table; two equal names are an error.
 int build_table(const hc_genome_contig* contigs, int32_t n, const hc_genome_result& res, Table& t)
@@ -187,8 +166,7 @@ std::string rname_of(const uint8_t* sam, int64_t sam_len, int64_t line)
 }
 
 // Table upload, resolve, buckets and picks on the device; fills res.contig_of, res.win_first and res.picked.
-int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const hc_sam_record* records, const int32_t* line_no,
-         const Table& t, int32_t n_contigs, uint64_t seed, int32_t pick_mode, uint32_t flags, hc_genome_result& res, Trace& tr)
+int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records, const int32_t* line_no, const Table& t, int32_t n_contigs, uint64_t seed, int32_t pick_mode, uint32_t flags, hc_genome_result& res, Trace& tr)
 {
     hipStream_t st = dev.stream;
     const int64_t total_len = t.off[size_t(n_contigs)];
@@ -282,7 +260,7 @@ int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const 
     int64_t* win_first = reinterpret_cast<int64_t*>(g_win.p + o_wf);
     a.win_first = win_first;
 
-    HIP_TRY(st, launch_resolve(a, st));
+    HIP_TRY(st, front.resolve(a, st));
     if (dev.n_records)
         HIP_TRY(st, hipMemcpyAsync(g_hrec.p, g_rec.p, sizeof(int32_t) * size_t(dev.n_records), hipMemcpyDeviceToHost, st));
     if (tr.on) {
@@ -345,11 +323,11 @@ int tile(const hcsam::Resident& dev, const uint8_t* sam, int64_t sam_len, const 
         if (at == line_no + dev.n_records || *at != key) return fail(HC_PHMM_EHIP, "genome caller: error word names no record");
         const size_t k = size_t(at - line_no);
         const hc_sam_record& r = records[k];
-        const std::string where = "line " + std::to_string(key) + ": ";
+        const std::string where = front.where(key);
         if ((err & 15ull) == kErrUnplaced) {
             const int32_t c = res.contig_of[k];
             if (c < 0)
-                return fail(HC_PHMM_EINVAL, where + "unplaced read, RNAME " + rname_of(sam, sam_len, r.line) +
+                return fail(HC_PHMM_EINVAL, where + "unplaced read, RNAME " + front.rname(r, k) +
                                                 " is not in the contig table");
             return fail(HC_PHMM_EINVAL, where + "unplaced read, POS " + std::to_string(r.pos) + " is 0 or past the " +
                                             std::to_string(res.ref_len[size_t(c)]) + " bases of contig " + res.names[size_t(c)]);
@@ -403,7 +381,7 @@ void print_site(std::string& out, const std::string& contig, const hc_gt_call_si
     out += std::to_string(s.a1) + '/' + std::to_string(s.a2) + ':' + std::to_string(s.genotype_quality) + '\n';
 }
 
-int run(const uint8_t* sam, int64_t sam_len, const hc_genome_contig* contigs, int32_t n_contigs, const Table& t, uint64_t seed,
+int run(Front& front, const hc_genome_contig* contigs, int32_t n_contigs, const Table& t, uint64_t seed,
         int32_t pick_mode, uint32_t flags, hc_genome_result& res)
 {
     Trace tr("HC_GENOME_TRACE", "[hc_genome]");
@@ -418,17 +396,17 @@ int run(const uint8_t* sam, int64_t sam_len, const hc_genome_contig* contigs, in
     {
         std::unique_lock<std::mutex> parser;   // held while the records and the text on the device are in use
         hcsam::Resident dev;
-        int rc = hcsam::parse_resident(sam, sam_len, &res.sam, parser, dev);
+        int rc = front.open(res, t, tr, parser, dev);
         if (rc) return rc;
-        tr.mark("parse");
         rc = hc_sam_result_records(res.sam, &records, &line_no, &n_records, &pool, nullptr, nullptr);
         if (rc) return rc;
         HIP_TRY(dev.stream, hipSetDevice(hcphmm::primary_device()));
-        rc = tile(dev, sam, sam_len, records, line_no, t, n_contigs, seed, pick_mode, flags, res, tr);
+        rc = tile(front, dev, records, line_no, t, n_contigs, seed, pick_mode, flags, res, tr);
         if (rc) return rc;
     }
 
-    // ---- the chain's structs: views into the caller's text and the parser's pool
+    // ---- the chain's structs: views into the front's text and the parser's pool
+    const uint8_t* sam = front.text();
     const int64_t total = res.win_first[size_t(n_windows)];
     std::vector<hc_prep_read> reads(static_cast<size_t>(total));
     std::vector<const uint8_t*> bases(static_cast<size_t>(total)), quals(static_cast<size_t>(total));
@@ -543,16 +521,36 @@ int check_name(const char* name, int32_t k)
     return HC_PHMM_OK;
 }
 
+// hc_genome_call's front: the SAM text, parsed by hc_sam_parse and left on the device.
+struct SamFront final : Front {
+    const uint8_t* sam;
+    int64_t sam_len;
+    SamFront(const uint8_t* s, int64_t n) : sam(s), sam_len(n) {}
+    int check() const override
+    {
+        return sam_len < 0 || (sam_len && !sam) ? fail(HC_PHMM_EINVAL, "null sam / negative length") : HC_PHMM_OK;
+    }
+    int open(hc_genome_result& res, const Table&, Trace& tr, std::unique_lock<std::mutex>& lk, hcsam::Resident& dev) override
+    {
+        const int rc = hcsam::parse_resident(sam, sam_len, &res.sam, lk, dev);
+        if (!rc) tr.mark("parse");
+        return rc;
+    }
+    hipError_t resolve(const GenomeArgs& a, hipStream_t st) override { return launch_resolve(a, st); }
+    const uint8_t* text() const override { return sam; }
+    std::string where(int64_t line_no) const override { return "line " + std::to_string(line_no) + ": "; }
+    std::string rname(const hc_sam_record& r, size_t) const override { return rname_of(sam, sam_len, r.line); }
+};
+
 }  // namespace
 
-extern "C" int hc_genome_call(const uint8_t* sam, int64_t sam_len, const hc_genome_contig* contigs, int32_t n_contigs,
-                              int32_t region_size, int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags_in,
-                              hc_genome_result** out)
+int hcgenome::genome_call(Front& front, const hc_genome_contig* contigs, int32_t n_contigs, int32_t region_size,
+                          int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags_in, hc_genome_result** out)
 {
     std::lock_guard<std::mutex> lk(g_st.mu);
     return call_frame(out, nullptr, [&](hc_genome_result& res) -> int {
         uint32_t flags = flags_in;
-        if (sam_len < 0 || (sam_len && !sam)) return fail(HC_PHMM_EINVAL, "null sam / negative length");
+        if (int rc = front.check()) return rc;
         if (!contigs) return fail(HC_PHMM_EINVAL, "null contigs");
         if (n_contigs < 1) return fail(HC_PHMM_EINVAL, "n_contigs below 1");
         if (n_contigs > HC_GENOME_MAX_CONTIGS) return fail(HC_PHMM_EINVAL, "more than " + std::to_string(HC_GENOME_MAX_CONTIGS) + " contigs");
@@ -577,8 +575,16 @@ extern "C" int hc_genome_call(const uint8_t* sam, int64_t sam_len, const hc_geno
         }
         Table t;
         if (int rc = build_table(contigs, n_contigs, res, t)) return rc;
-        return run(sam, sam_len, contigs, n_contigs, t, seed, pick_mode, flags, res);
+        return run(front, contigs, n_contigs, t, seed, pick_mode, flags, res);
     });
+}
+
+extern "C" int hc_genome_call(const uint8_t* sam, int64_t sam_len, const hc_genome_contig* contigs, int32_t n_contigs,
+                              int32_t region_size, int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags,
+                              hc_genome_result** out)
+{
+    SamFront front(sam, sam_len);
+    return genome_call(front, contigs, n_contigs, region_size, padding_size, seed, pick_mode, flags, out);
 }
 
 extern "C" int hc_genome_result_vcf(const hc_genome_result* res, const char** text, int64_t* length, int32_t* n_windows,

@@ -31,13 +31,6 @@
 using namespace hcsam;
 using namespace stage_host;
 
-struct hc_sam_result {
-    std::vector<hc_sam_record> records;
-    std::vector<int32_t> line_no;
-    std::vector<uint32_t> pool;
-    int32_t n_header_lines = 0;
-};
-
 namespace {
 
 Buf g_text, g_chunks, g_lines, g_out, g_stage{nullptr, 0, true}, g_hback{nullptr, 0, true}, g_hsmall{nullptr, 0, true};
@@ -67,6 +60,29 @@ const char* error_text(int64_t code)
     }
 }
 
+}  // namespace
+
+stage_host::Stage& hcsam::parser_stage() { return g_st; }
+
+int hcsam::upload(const uint8_t* bytes, int64_t len, size_t room, const uint8_t*& on_device)
+{
+    const size_t stage = std::min(stage_bytes(), size_t(len));
+    int rc = reserve(g_text, room, "SAM text on the device");
+    if (rc) return rc;
+    rc = reserve(g_stage, stage, "SAM text staging");
+    if (rc) return rc;
+    for (int64_t off = 0; off < len; off += int64_t(stage)) {
+        const size_t n = size_t(std::min<int64_t>(int64_t(stage), len - off));
+        std::memcpy(g_stage.p, bytes + off, n);
+        HIP_TRY(g_st.stream, hipMemcpyAsync(g_text.p + off, g_stage.p, n, hipMemcpyHostToDevice, g_st.stream));
+        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));   // the block is reused by the next piece
+    }
+    on_device = reinterpret_cast<const uint8_t*>(g_text.p);
+    return HC_PHMM_OK;
+}
+
+namespace {
+
 int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
 {
     Trace tr("HC_SAM_TRACE", "[hc_sam]");
@@ -75,20 +91,10 @@ int run(const uint8_t* text, int64_t len, hc_sam_result& res, Resident& dev)
     a.n_chunks = (len + kChunkBytes - 1) / kChunkBytes;
 
     // ---- the text, through the staging block
-    const size_t stage = std::min(stage_bytes(), size_t(len));
-    int rc = reserve(g_text, size_t(a.n_chunks) * kChunkBytes, "SAM text on the device");
-    if (rc) return rc;
-    rc = reserve(g_stage, stage, "SAM text staging");
+    int rc = upload(text, len, size_t(a.n_chunks) * kChunkBytes, a.text);
     if (rc) return rc;
     rc = reserve(g_hsmall, 256, "SAM parser totals");
     if (rc) return rc;
-    for (int64_t off = 0; off < len; off += int64_t(stage)) {
-        const size_t n = size_t(std::min<int64_t>(int64_t(stage), len - off));
-        std::memcpy(g_stage.p, text + off, n);
-        HIP_TRY(g_st.stream, hipMemcpyAsync(g_text.p + off, g_stage.p, n, hipMemcpyHostToDevice, g_st.stream));
-        HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));   // the block is reused by the next piece
-    }
-    a.text = reinterpret_cast<const uint8_t*>(g_text.p);
     tr.mark("upload");
 
     // ---- line starts: count and scan

@@ -1,13 +1,24 @@
 // What the contig caller (contig_engine.cpp) and the genome caller
 // (genome_engine.cpp) share with the SAM parser (sam_engine.cpp): a parse that
 // leaves its records and the text on the device and hands the parser's lock to
-// the caller.
+// the caller. The BAM front (bam_engine.cpp) fills the same result object from
+// its own kernels, under the parser's lock and on the parser's stream, and sends
+// its file up through the parser's staging block.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <vector>
 
 #include "../../include/hc_sam.h"
+#include "stage_host.hpp"
+
+struct hc_sam_result {
+    std::vector<hc_sam_record> records;
+    std::vector<int32_t> line_no;
+    std::vector<uint32_t> pool;
+    int32_t n_header_lines = 0;
+};
 
 namespace hcsam {
 
@@ -24,5 +35,12 @@ struct Resident {
 // records and the text on the device; they stay as they are until `lk` is released.
 int parse_resident(const uint8_t* text, int64_t text_len, hc_sam_result** out, std::unique_lock<std::mutex>& lk,
                    Resident& dev);
+
+// The parser's lock, stream and buffers.
+stage_host::Stage& parser_stage();
+// With the parser's lock held and the stage initialised: `bytes` to the device
+// through the pinned staging block of HC_SAM_STAGE_BYTES, piece after piece, into
+// the parser's text buffer of at least `room` >= len bytes.
+int upload(const uint8_t* bytes, int64_t len, size_t room, const uint8_t*& on_device);
 
 }  // namespace hcsam
