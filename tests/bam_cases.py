@@ -14,10 +14,39 @@ malformed_cases(): (file, the 0-based member the error names, its BgzfError code
 A member's whole size is at most 65 536 bytes (BSIZE has 16 bits), so a stored
 block of 65 535 bytes cannot stand in a BGZF member: the largest stored block
 here has 65 000 bytes, with a second block behind it in the same member.
+Every stream of bgzf_cases() is zlib's, and zlib uses a narrow part of the
+format: in these files no code longer than 12 bits, always two distance codes
+at least, the two alphabets' lengths coded apart, no distance above 32 503
+(zlib's window stops 262 bytes short of 32 768, so second_half_repeats, whose
+second half repeats the first 32 768 bytes back, is not copied at that distance).
+
+What zlib never writes (what each input exercises is asserted from a census of
+its streams in test_bgzf_census.py):
+written_cases(): name -> (raw DEFLATE stream, bytes) from deflate_writer:
+    deep15                     code lengths 1...15, 15 in both alphabets, the 15-bit codes on end-of-block,
+                               symbol 285 and distance symbols 28 and 29, HCLEN 19, a last match of 258 at
+                               distance 32 768
+    every_code_fixed / _dynamic   all 29 length and 30 distance symbols with their extra bits all zero and all one
+                               (258 as symbol 284 + 31 too), distance 32 768; _dynamic under HLIT = HDIST = 29
+    overlaps                   distances 1...66, 127, 128, 129, 257, each with lengths 3, 64, 65, 258
+    no_distance_code, one_distance_code, hlit_0
+    run_across_alphabets, zero_run_across_alphabets   a run code 16 / 18 from the literal/length lengths into
+                               the distance lengths
+    tiny_blocks                1 504 blocks: fixed, dynamic, stored, empty stored in turn, matches across their
+                               borders, the last an empty stored block
+    ends_on_a_match            ISIZE 65 536, the last token a match of 258
+    stored_then_far_match      a match at distance 20 000 to the member's first byte, through a stored block
+written_file(): (file, bytes), every case a member, three of them again behind members of odd sizes.
+alignment_file(): (file, bytes), 118 small zlib members, every out_off & 15 against ISIZE 1, 2, 15, 16, 17, 31, 33.
+written_malformed_cases(): as malformed_cases(), the DEFLATE errors that one is without.
+libdeflate_members(): the streams of tests/golden/libdeflate_members.npz, a second producer's.
+mutants(n, seed): seeded edits of small streams with zlib's verdict (zlib_verdict) as the expected one.
+bgzf(..., compress=) / to_bam(..., compress=): members from another writer, e.g. written_compress.
 """
 from __future__ import annotations
 
 import functools
+import os
 import random
 import struct
 import zlib
@@ -52,9 +81,14 @@ def good_member(data: bytes, **kw) -> bytes:
     return member(deflate(data, **kw), zlib.crc32(data), len(data))
 
 
-def bgzf(data: bytes, member_size=65280, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, mem_level=8, eof=True) -> bytes:
-    out = b"".join(good_member(data[k:k + member_size], level=level, strategy=strategy, mem_level=mem_level)
-                   for k in range(0, len(data), member_size))
+def bgzf(data: bytes, member_size=65280, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, mem_level=8, eof=True,
+         compress=None) -> bytes:
+    """compress: bytes -> a raw DEFLATE stream, in place of zlib's."""
+    if compress is None:
+        def compress(piece):
+            return deflate(piece, level=level, strategy=strategy, mem_level=mem_level)
+    out = b"".join(member(compress(data[k:k + member_size]), zlib.crc32(data[k:k + member_size]),
+                          len(data[k:k + member_size])) for k in range(0, len(data), member_size))
     return out + (EOF_MARKER if eof else b"")
 
 
@@ -87,23 +121,31 @@ def first_block_type(stream: bytes) -> int:
 
 
 class Bits:
-    """A DEFLATE bit writer: put() least significant bit first, code() a Huffman code, most significant first."""
+    """A DEFLATE bit writer: put() least significant bit first, code() a Huffman code, most significant first.
+    n is the number of bits written so far."""
 
     def __init__(self):
-        self.acc, self.n = 0, 0
+        self.buf, self.acc, self.k = bytearray(), 0, 0
+
+    @property
+    def n(self):
+        return 8 * len(self.buf) + self.k
 
     def put(self, value, n):
-        self.acc |= value << self.n
-        self.n += n
+        self.acc |= value << self.k
+        self.k += n
+        if self.k >= 8:
+            whole = self.k >> 3
+            self.buf += (self.acc & ((1 << 8 * whole) - 1)).to_bytes(whole, "little")
+            self.acc >>= 8 * whole
+            self.k &= 7
         return self
 
     def code(self, code, n):
-        for k in range(n - 1, -1, -1):
-            self.put((code >> k) & 1, 1)
-        return self
+        return self.put(int(format(code, f"0{n}b")[::-1], 2), n) if n else self
 
     def bytes(self):
-        return self.acc.to_bytes((self.n + 7) // 8, "little")
+        return bytes(self.buf) + (bytes([self.acc & 255]) if self.k else b"")
 
 
 def _rng_bytes(seed, n, alphabet=None):
@@ -209,6 +251,416 @@ def malformed_offset(member_index: int) -> int:
     return sum(len(good_member(text[k * 30000:(k + 1) * 30000])) for k in range(member_index))
 
 
+# ---- streams that zlib never writes ---------------------------------------------------------
+
+def zlib_verdict(stream: bytes):
+    """What zlib makes of a raw DEFLATE stream as a BGZF member's: its bytes when decompressobj(-15) reaches the
+    end of the last block with at most 65 536 bytes, None when it refuses or the stream ends early."""
+    d = zlib.decompressobj(-15)
+    try:
+        data = d.decompress(stream, 65537)
+    except zlib.error:
+        return None
+    return data if d.eof and len(data) <= 65536 else None
+
+
+def zlib_overflows(stream: bytes) -> bool:
+    """Whether zlib, fed a byte at a time, has given more than 65 536 bytes when the stream ends or zlib refuses
+    it: the one way in which a member of ISIZE 65 536 with a stream that zlib refuses may end with ERR_COUNT."""
+    d, n = zlib.decompressobj(-15), 0
+    try:
+        for k in range(len(stream)):
+            n += len(d.decompress(stream[k:k + 1]))
+            if n > 65536:
+                return True
+    except zlib.error:
+        pass
+    return False
+
+
+def lz_tokens(data: bytes):
+    """Tokens of deflate_writer for data: a greedy matcher on the last place of every three bytes."""
+    toks, last, k, n = [], {}, 0, len(data)
+    while k < n:
+        key = data[k:k + 3]
+        cand = last.get(key) if len(key) == 3 else None
+        length = 0
+        if cand is not None and k - cand <= 32768:
+            while length < 258 and k + length < n and data[cand + length] == data[k + length]:
+                length += 1
+        if length >= 3:
+            toks.append((length, k - cand))
+            last[key] = k
+            k += length
+        else:
+            last[key] = k
+            toks.append(data[k])
+            k += 1
+    return toks
+
+
+def written_compress(data: bytes) -> bytes:
+    """data as one dynamic block from the writer: complete(., 15) lengths over the symbols lz_tokens(data) uses,
+    the shortest codes on the most used."""
+    import deflate_writer as W
+    toks = lz_tokens(data)
+    lit, dist = W.symbols_of(toks)
+    return W.dynamic(Bits(), toks, W.lens_by_use(lit), W.lens_by_use(dist), True).bytes()
+
+
+def _deep15_lens():
+    lit = {c: k + 1 for k, c in enumerate(b"ACGTNacgtn\t\n01")}
+    lit[256] = lit[285] = 15
+    dist = {14 + k: k + 1 for k in range(14)}
+    dist[28] = dist[29] = 15
+    return lit, dist
+
+
+def _every_code_tokens():
+    import deflate_writer as W
+    r = random.Random(13)
+    toks, pos = list(range(256)), 256
+    while pos < 32768:
+        toks.append((258, r.choice((256, 255, 131, 64, 7))))
+        pos += 258
+    lengths = [(W.LEN_BASE[k] + hi * ((1 << W.LEN_EXTRA[k]) - 1), 257 + k) for k in range(29) for hi in (0, 1)]
+    dists = [W.DIST_BASE[d] + hi * ((1 << W.DIST_EXTRA[d]) - 1) for d in range(30) for hi in (0, 1)]
+    for i, dist in enumerate(dists):
+        length, s = lengths[i % len(lengths)]
+        toks += [(length, dist, s), r.randrange(256)]
+    return toks
+
+
+@functools.lru_cache(maxsize=None)
+def written_cases():
+    """name -> (raw DEFLATE stream, its bytes), every stream from deflate_writer; see the module's docstring of
+    test_bgzf_census.py for the property each one carries."""
+    import deflate_writer as W
+    out = {}
+
+    def add(name, bits, toks):
+        out[name] = (bits.bytes(), W.expand(toks))
+
+    # deep15
+    r = random.Random(11)
+    lit_lens, dist_lens = _deep15_lens()
+    lits = [c for c in lit_lens if c < 256]
+    toks, pos = list(lits), len(lits)
+
+    def far(d):
+        return W.DIST_BASE[d] + r.randrange(1 << W.DIST_EXTRA[d])
+    while pos < 33000:
+        toks += r.choices(lits, weights=[2.0 ** -k for k in range(len(lits))], k=40)
+        pos += 40
+        dist = far(r.randrange(14, 30))
+        if dist <= pos and r.random() < 0.3:
+            toks.append((258, dist))
+            pos += 258
+    for d in range(14, 30):
+        toks += [(258, far(d)), r.choice(lits)]
+    pos = len(W.expand(toks))
+    assert pos >= 32768
+    toks.append((258, 32768))
+    add("deep15", W.dynamic(Bits(), toks, lit_lens, dist_lens, True), toks)
+
+    # every_code_*
+    toks = _every_code_tokens()
+    add("every_code_fixed", W.fixed(Bits(), toks, True), toks)
+    add("every_code_dynamic", W.dynamic(Bits(), toks, dict(zip(range(286), W.complete(286, 15))),
+                                        dict(zip(range(30), W.complete(30, 15))), True), toks)
+
+    # overlaps
+    r = random.Random(14)
+    toks = list(r.randbytes(300))
+    for dist in list(range(1, 67)) + [127, 128, 129, 257]:
+        for length in (3, 64, 65, 258):
+            toks += [(length, dist), r.randrange(256), r.randrange(256)]
+    add("overlaps", W.fixed(Bits(), toks, True), toks)
+
+    # no_distance_code: HDIST = 0 and that one length 0
+    toks = list(_texty(15, 701))
+    add("no_distance_code", W.dynamic(Bits(), toks, W.lens_by_use(W.symbols_of(toks)[0]), {}, True, ndist=1), toks)
+
+    # one_distance_code: distance symbol 9 (25...32) with one bit
+    r = random.Random(16)
+    toks = list(r.randbytes(45))
+    for length in (3, 258, 10, 64, 31, 32, 33, 4, 258, 200):
+        toks += [(length, 25 + r.randrange(8)), r.randrange(256)]
+    add("one_distance_code", W.dynamic(Bits(), toks, W.lens_by_use(W.symbols_of(toks)[0]), {9: 1}, True), toks)
+
+    # run_across_alphabets: ... 257, 258, 259 | 0, 1, 2 ... all of three bits
+    r = random.Random(17)
+    toks = list(b"abcdabdcbadcdcba")
+    for _ in range(60):
+        toks += [r.choice(b"abcd"), (r.choice((3, 4, 5)), r.randrange(1, 17))]
+    add("run_across_alphabets", W.dynamic(Bits(), toks, {s: 3 for s in (97, 98, 99, 100, 256, 257, 258, 259)},
+                                          {d: 3 for d in range(8)}, True), toks)
+
+    # zero_run_across_alphabets: zeros from 258 to 269 and on distance symbols 0 to 9
+    toks = list(b"ab" * 20 + b"ba" * 15)
+    for _ in range(30):
+        toks += [r.choice(b"ab"), (3, r.randrange(33, 65))]
+    add("zero_run_across_alphabets", W.dynamic(Bits(), toks, {97: 2, 98: 2, 256: 2, 257: 2}, {10: 1, 11: 1}, True, nlen=270),
+        toks)
+
+    # hlit_0
+    toks = list(_texty(18, 333))
+    add("hlit_0", W.dynamic(Bits(), toks, W.lens_by_use(W.symbols_of(toks)[0]), {0: 1, 1: 1}, True), toks)
+
+    # tiny_blocks: fixed, dynamic, stored, empty stored, 376 times
+    r = random.Random(19)
+    bits, whole = Bits(), []
+    for i in range(376):
+        pos = len(whole) if i < 3 else 99            # enough behind for every distance below
+        toks = ([(3 + i % 5, 4 + i % 9)] if pos > 12 else []) + [r.randrange(256), r.randrange(256)]
+        W.fixed(bits, toks, False)
+        whole += toks
+        toks = [(3 + i % 4, 2 + i % 3), r.randrange(256), (5, 1 + i % 7)]
+        lit, dist = W.symbols_of(toks)
+        W.dynamic(bits, toks, W.lens_by_use(lit), W.lens_by_use(dist), False)
+        whole += toks
+        raw = r.randbytes(3)
+        W.stored(bits, raw, False)
+        whole += list(raw)
+        W.stored(bits, b"", i == 375)
+    add("tiny_blocks", bits, whole)
+
+    # ends_on_a_match
+    r = random.Random(20)
+    toks = list(_texty(21, 2000))
+    pos = 2000
+    while pos + 259 <= 65536 - 258:
+        toks += [(258, r.randrange(1, min(pos, 32768) + 1)), r.randrange(256)]
+        pos += 259
+    toks += list(r.randbytes(65536 - 258 - pos)) + [(258, 1000)]
+    lit, dist = W.symbols_of(toks)
+    add("ends_on_a_match", W.dynamic(Bits(), toks, W.lens_by_use(lit), W.lens_by_use(dist), True), toks)
+
+    # a match that reaches the member's first byte from deep inside, through a stored block
+    raw = _rng_bytes(22, 20000)
+    toks = [(258, 20000), 120]
+    add("stored_then_far_match", W.fixed(W.stored(Bits(), raw, False), toks, True), list(raw) + toks)
+    return out
+
+
+def file_of(streams_and_bytes, eof=True):
+    """(file, bytes) of [(raw DEFLATE stream, its bytes)]: a member each, then the end-of-file member."""
+    pairs = list(streams_and_bytes)
+    file = b"".join(member(s, zlib.crc32(d), len(d)) for s, d in pairs) + (EOF_MARKER if eof else b"")
+    return file, b"".join(d for _, d in pairs)
+
+
+AGAIN = ("deep15", "overlaps", "one_distance_code")
+
+
+def written_names():
+    """The case of every member of written_file() but the last."""
+    return list(written_cases()) + list(AGAIN)
+
+
+@functools.lru_cache(maxsize=None)
+def written_file():
+    """(file, bytes): every case of written_cases() as a member, then AGAIN behind members of odd sizes."""
+    c = written_cases()
+    return file_of(c[name] for name in written_names())
+
+
+ALIGN_CLASSES = (1, 2, 15, 16, 17, 31, 33)
+ALIGN_STEPS = (63, 64, 65, 127, 128, 129)
+
+
+@functools.lru_cache(maxsize=None)
+def alignment_file():
+    """(file, bytes): small zlib members such that every out_off & 15 meets every ISIZE of ALIGN_CLASSES. Pairs
+    of 16 + 1 and of 2 + 15 bytes move the offset by 17, members of 17, 31 and 33 bytes by an odd step, so 16
+    rounds of each pass every residue; then the ISIZEs at which the CRC32's slice size steps."""
+    sizes = [16, 1] * 16 + [2, 15] * 16 + [17] * 16 + [31] * 16 + [33] * 16 + list(ALIGN_STEPS)
+    r = random.Random(23)
+    pairs = []
+    for k, n in enumerate(sizes):
+        data = r.randbytes(n) if k % 2 else bytes(r.choices(b"AC", k=n))
+        pairs.append((deflate(data, level=(6, 0, 9, 1)[k % 4], strategy=zlib.Z_FIXED if k % 3 == 0 else zlib.Z_DEFAULT_STRATEGY),
+                      data))
+    return file_of(pairs)
+
+
+@functools.lru_cache(maxsize=None)
+def _three_good():
+    text = _texty(7, 90000)
+    return [good_member(text[k:k + 30000]) for k in (0, 30000, 60000)]
+
+
+def _as_second(m: bytes) -> bytes:
+    g = _three_good()
+    return g[0] + m + g[2] + EOF_MARKER
+
+
+@functools.lru_cache(maxsize=None)
+def written_malformed_cases():
+    """name -> (file, the 0-based member the message names, the BgzfError code): one bad member between two good
+    ones, as in malformed_cases(). zlib refuses the stream of every case but the ERR_COUNT ones, whose streams
+    are well formed and whose ISIZE is wrong."""
+    import deflate_writer as W
+    out = {}
+
+    def add(name, stream, code, isize=100, crc=0):
+        stream = stream.bytes() if isinstance(stream, Bits) else stream
+        out[name] = (_as_second(member(stream, crc, isize)), 1, code)
+
+    def pad(bits):
+        return bits.put(0, 32)
+    lit8 = {s: 3 for s in (97, 98, 99, 100, 256, 257, 258, 259)}
+    dist8 = {d: 3 for d in range(8)}
+    fl, fd = W.canonical(W.FIXED_LIT), W.canonical(W.FIXED_DIST)
+    some = list(b"abcdabcd")
+
+    # ERR_STREAM
+    add("fixed_symbol_286", pad(W.body(Bits().put(1, 1).put(1, 2), some, fl, fd, end=False).code(*fl[286])), ERR_STREAM)
+    b = W.body(Bits().put(1, 1).put(1, 2), some, fl, fd, end=False).code(*fl[257]).code(*fd[30])
+    add("fixed_distance_30", pad(b), ERR_STREAM)
+    add("btype_3", pad(W.fixed(Bits(), some, False).put(1, 1).put(3, 2)), ERR_STREAM)
+    add("stored_nlen_wrong", W.stored(Bits(), b"stored bytes", True, nlen_xor=0xFFFE), ERR_STREAM)
+    cl = {3: 1, 16: 2, 18: 2}
+    b = W.header(Bits(), True, 3, 7, cl, [(16, 3)] + [(3, 0)] * 262)
+    add("run_16_first", pad(b), ERR_STREAM)
+    tokens = W.run_lengths([lit8.get(s, 0) for s in range(260)] + [3] * 8)
+    assert tokens[-1] == (16, 2)                 # the last run, made one longer than the array has room for
+    b = W.header(Bits(), True, 3, 7, W.code_length_code(tokens), tokens[:-1] + [(16, 3)])
+    add("run_past_the_end", pad(W.body(b, some, W.canonical(lit8), W.canonical(dist8))), ERR_STREAM)
+    add("hlit_30", pad(W.dynamic(Bits(), some, lit8, dist8, True, nlen=287)), ERR_STREAM)
+    add("hdist_30", pad(W.dynamic(Bits(), some, lit8, dist8, True, ndist=31)), ERR_STREAM)
+    no_end = {s: 3 for s in (97, 98, 99, 100, 101, 257, 258, 259)}
+    b = W.body(W.dynamic_header(Bits(), no_end, dist8, True), some, W.canonical(no_end), W.canonical(dist8), end=False)
+    add("no_end_of_block", pad(b), ERR_STREAM)
+    three = {97: 2, 98: 2, 256: 2}
+    b = W.body(W.dynamic_header(Bits(), three, dist8, True), list(b"abab"), W.canonical(three), W.canonical(dist8))
+    add("incomplete_literal_set", pad(b), ERR_STREAM)
+    b = W.body(W.dynamic_header(Bits(), lit8, {}, True, ndist=1), some, W.canonical(lit8), {}, end=False)
+    add("match_without_distance_code", pad(b.code(*W.canonical(lit8)[257])), ERR_STREAM)
+    b = W.body(W.dynamic_header(Bits(), lit8, {2: 1}, True), some, W.canonical(lit8), {}, end=False)
+    add("absent_code_of_one_code_set", pad(b.code(*W.canonical(lit8)[257]).put(1, 1)), ERR_STREAM)
+
+    # ERR_EARLY
+    add("stored_len_past_input", W.stored(Bits(), b"0123456789", True).bytes()[:-3], ERR_EARLY)
+    add("last_block_never_marked", W.fixed(W.fixed(Bits(), some, False), some, False), ERR_EARLY)
+    lit15, dist15 = _deep15_lens()
+    head = W.dynamic_header(Bits(), lit15, dist15, True)
+    whole = W.body(W.dynamic_header(Bits(), lit15, dist15, True), list(b"ACGT"), W.canonical(lit15), W.canonical(dist15))
+    assert head.n > 8 * 12
+    for cut in (1, 2, 3, 5, 8, (head.n + 7) // 8 - 1):
+        add(f"header_cut_at_{cut}" if cut <= 8 else "header_cut_a_byte_before_its_end", whole.bytes()[:cut], ERR_EARLY)
+
+    # ERR_DISTANCE
+    raw = _rng_bytes(22, 20000)
+    add("distance_one_past_the_start", W.fixed(W.stored(Bits(), raw, False), [(258, 20001), 120], True), ERR_DISTANCE,
+        isize=20259)
+
+    # ERR_COUNT: zlib accepts the stream
+    def count(name, stream, data, isize):
+        assert zlib_verdict(stream.bytes()) == data and isize < len(data)
+        add(name, stream, ERR_COUNT, isize=isize, crc=zlib.crc32(data[:isize]))
+    count("stored_larger_than_isize", W.stored(Bits(), raw[:500], True), raw[:500], 499)
+    toks = list(raw[:40])
+    count("literal_at_isize", W.fixed(Bits(), toks, True), W.expand(toks), 39)
+    toks = list(raw[:300]) + [(258, 300)]
+    count("match_across_isize", W.fixed(Bits(), toks, True), W.expand(toks), 400)
+    stream, data = written_cases()["one_distance_code"]
+    out["one_distance_code_isize_one_short"] = (_as_second(member(stream, zlib.crc32(data[:-1]), len(data) - 1)), 1, ERR_COUNT)
+    return out
+
+
+GOLDEN_LIBDEFLATE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "libdeflate_members.npz")
+
+
+@functools.lru_cache(maxsize=None)
+def libdeflate_members():
+    """[(name, raw DEFLATE stream, its bytes)] of tests/golden/libdeflate_members.npz, which
+    tests/golden/make_libdeflate_golden.py wrote with libdeflate; the library is not needed to read it."""
+    import numpy as np
+    g = np.load(GOLDEN_LIBDEFLATE, allow_pickle=False)
+    names, of = [n.decode() for n in g["names"]], g["stream_off"]
+    plain = {n.decode(): g["plain"][g["plain_off"][k]:g["plain_off"][k + 1]].tobytes() for k, n in enumerate(g["inputs"])}
+    return [(n, g["streams"][of[k]:of[k + 1]].tobytes(), plain[n.rsplit("_level_", 1)[0]]) for k, n in enumerate(names)]
+
+
+def libdeflate_inputs():
+    """name -> bytes: what make_libdeflate_golden.py compresses."""
+    import genome_cases as GC
+    whole = inflate(to_bam(GC.genome()["sam"]))
+    text = _texty(31, 70300)
+    return dict(texty_65000=text[:65000], texty_5000=text[65000:70000], texty_300=text[70000:], acgt=_rng_bytes(32, 40000, b"ACGT"),
+                run=b"z" * 65536, ab=b"ab" * 30000, all_bytes=bytes(range(256)), bam=whole[:60000])
+
+
+@functools.lru_cache(maxsize=None)
+def mutant_seeds():
+    """Small well-formed streams of 40 to 3 000 bytes: zlib at levels 1, 6 and 9 and with Z_FIXED, the writer's, the
+    fixture's."""
+    out = []
+    for k, n in enumerate((150, 400, 900, 2000, 4000, 7000)):
+        data = _texty(40 + k, n)
+        out += [deflate(data, level=1), deflate(data, level=6), deflate(data, level=9), deflate(data, strategy=zlib.Z_FIXED)]
+    out += [s for s, _ in written_cases().values()]
+    out += [s for _, s, _ in libdeflate_members()]
+    out = [s for s in out if 40 <= len(s) <= 3000]
+    assert len(out) >= 30
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def mutants(n: int, seed: int):
+    """n streams [(stream, zlib's bytes or None)]: a seed with 1 to 3 edits, each a bit flip (half of them in the
+    first 60 bytes), a truncation or a byte replaced. The verdict is zlib_verdict()'s."""
+    r = random.Random(seed)
+    seeds, out = mutant_seeds(), []
+    for _ in range(n):
+        s = bytearray(r.choice(seeds))
+        for _ in range(r.randint(1, 3)):
+            kind = r.random()
+            if kind < 0.6:
+                at = r.randrange(min(60, len(s))) if r.random() < 0.5 else r.randrange(len(s))
+                s[at] ^= 1 << r.randrange(8)
+            elif kind < 0.75:
+                del s[r.randrange(max(1, len(s) - 40), len(s)):]
+            else:
+                s[r.randrange(len(s))] = r.randrange(256)
+            if not s:
+                s = bytearray(b"\0")
+        out.append((bytes(s), zlib_verdict(bytes(s))))
+    return out
+
+
+# what hc_bgzf_inflate's message says behind "member K at offset N: " for a stream's error
+ERR_TEXT = {ERR_STREAM: "a malformed DEFLATE stream", ERR_EARLY: "the DEFLATE stream ends early",
+            ERR_COUNT: "the DEFLATE stream does not produce ISIZE bytes",
+            ERR_DISTANCE: "a back-reference before the member's first byte"}
+
+
+@functools.lru_cache(maxsize=None)
+def device_refusals(kind: str):
+    """The malformed inputs of the device tests, in groups that one child process takes in turn:
+    [[(name, file, the texts the message may end with)]]. "written": written_malformed_cases() in 4 groups;
+    "mutants": the first 64 mutants of mutants(2000, 1) that zlib refuses, each between two good members, in 4
+    groups of 16 (ERR_COUNT only where zlib_overflows() says so)."""
+    if kind == "written":
+        rows = [(name, file, (ERR_TEXT[code],)) for name, (file, _, code) in sorted(written_malformed_cases().items())]
+        size = 7
+    else:
+        refused = [(k, s) for k, (s, d) in enumerate(mutants(2000, 1)) if d is None][:64]
+        rows = [(f"mutant {k}", _as_second(mutant_member(s, None)),
+                 tuple(ERR_TEXT[c] for c in (ERR_STREAM, ERR_EARLY, ERR_DISTANCE) + ((ERR_COUNT,) if zlib_overflows(s) else ())))
+                for k, s in refused]
+        size = 16
+        assert len(rows) == 64
+    return [rows[k:k + size] for k in range(0, len(rows), size)]
+
+
+def mutant_member(stream: bytes, data) -> bytes:
+    """A mutant as a member: zlib's CRC32 and ISIZE where zlib accepts it; ISIZE 65 536 where it does not, so
+    that the inflater walks the stream as far as it goes."""
+    return member(stream, 0, 65536) if data is None else member(stream, zlib.crc32(data), len(data))
+
+
 # ---- BAM -------------------------------------------------------------------------------
 
 def record(ref_id=0, pos=99, mapq=60, flag=0, cigar=(), next_ref_id=-1, next_pos=-1, tlen=0, name=b"q", seq="", qual=None,
@@ -288,7 +740,7 @@ def refs_of(fields):
 
 
 def to_bam(sam_text: bytes, ref_names_and_lengths=None, member_size=65280, level=6, strategy=zlib.Z_DEFAULT_STRATEGY,
-           mem_level=8) -> bytes:
+           mem_level=8, compress=None) -> bytes:
     header, fields = split_sam(sam_text)
     refs = refs_of(fields) if ref_names_and_lengths is None else list(ref_names_and_lengths)
     where = {(n if isinstance(n, str) else n.decode("latin-1")): k for k, (n, _) in enumerate(refs)}
@@ -300,7 +752,7 @@ def to_bam(sam_text: bytes, ref_names_and_lengths=None, member_size=65280, level
         recs.append(record(ref_id=rid, pos=int(f[3]) - 1, mapq=int(f[4]), flag=int(f[1]), cigar=cigar_words(f[5]),
                            next_ref_id=nid, next_pos=int(f[7]) - 1, tlen=int(f[8]), name=f[0].encode("latin-1"), seq=f[9],
                            qual=None if f[10] == "*" else bytes(ord(c) - 33 for c in f[10])))
-    return bgzf(bam_stream(header, refs, recs), member_size, level, strategy, mem_level)
+    return bgzf(bam_stream(header, refs, recs), member_size, level, strategy, mem_level, compress=compress)
 
 
 def parse_bam(stream: bytes):

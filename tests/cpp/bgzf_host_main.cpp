@@ -13,8 +13,14 @@
 // OUT.bin: the inflated bytes of the members in front of the first error.
 // stdout:  one line "M index coff out_off isize" per such member, then
 //          "E member code coff" for the first error (hcbgzf::BgzfError) or "OK".
+//
+//   bgzf_host_main --batch DIR N
+//
+// The files DIR/0.bgzf ... DIR/<N-1>.bgzf in one run: DIR/<k>.bin as OUT.bin
+// above, and on stdout the last line alone for every file, in order.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iterator>
@@ -25,16 +31,16 @@
 
 using namespace hcbgzf;
 
-int main(int argc, char** argv)
+// One file. With `rows`, the member lines go to stdout; the last line ("E ..." or "OK") always does.
+static int run(const char* in_path, const char* out_path, bool rows)
 {
-    if (argc != 3) return 2;
-    std::ifstream in(argv[1], std::ios::binary);
+    std::ifstream in(in_path, std::ios::binary);
     if (!in) return 2;
     const std::string whole((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
     const int64_t len = int64_t(whole.size());
     std::unique_ptr<uint8_t[]> file(new uint8_t[size_t(len)]);
     std::memcpy(file.get(), whole.data(), size_t(len));
-    std::ofstream out(argv[2], std::ios::binary);
+    std::ofstream out(out_path, std::ios::binary);
     std::unique_ptr<BgzfWork> work(new BgzfWork);
     uint32_t table[256];
     for (uint32_t i = 0; i < 256; ++i) table[i] = bgzf_crc_entry(i);
@@ -58,7 +64,7 @@ int main(int argc, char** argv)
             }
             if (!err) {
                 out.write(reinterpret_cast<const char*>(bytes.get() + shift), m.isize);
-                std::printf("M %d %lld %lld %d\n", index, (long long)m.coff, (long long)m.out_off, m.isize);
+                if (rows) std::printf("M %d %lld %lld %d\n", index, (long long)m.coff, (long long)m.out_off, m.isize);
             }
         }
         if (err) {
@@ -70,4 +76,19 @@ int main(int argc, char** argv)
     }
     std::printf("OK\n");
     return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc == 4 && std::strcmp(argv[1], "--batch") == 0) {
+        const int count = std::atoi(argv[3]);
+        for (int k = 0; k < count; ++k) {
+            const std::string stem = std::string(argv[2]) + "/" + std::to_string(k);
+            const int rc = run((stem + ".bgzf").c_str(), (stem + ".bin").c_str(), false);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    if (argc != 3) return 2;
+    return run(argv[1], argv[2], true);
 }

@@ -7,9 +7,11 @@ borders): every field of the records equals the SAM parser's parse of
 sam_of(bam), the pool word for word, and the bytes the records view in the
 bases buffer are the SEQ and QUAL tokens of that text. Lines that BAM cannot
 hold (MAPQ above 255, POS above 2^31, SEQ or QUAL "*") are left out of the grid.
-Then what has no SAM twin (l_seq 0, QUAL 0xFF, a quality of 94, all 16 nibble
+The genome text once more in members that zlib did not write (one dynamic block
+each from tests/deflate_writer.py, code lengths up to 15). Then what has no SAM twin (l_seq 0, QUAL 0xFF, a quality of 94, all 16 nibble
 codes, refID -1, pos -1, an empty BAM) and every BAM error of the header."""
 import struct
+import zlib
 
 import numpy as np
 import pytest
@@ -83,6 +85,35 @@ def test_records_equal_the_sam_parse_of_the_canonical_text(expected, name, membe
     assert g["header"] == header and g["refs"] == BC.refs_of(fields)
     where = {n: k for k, (n, _) in enumerate(g["refs"])}
     assert g["ref_id"].tolist() == [where.get(f[2], -1) for f in fields]
+
+
+def test_members_from_another_writer(expected):
+    """The genome text in members that zlib did not write: each one dynamic block from deflate_writer with
+    complete(., 15) code lengths over the symbols it uses (bam_cases.written_compress)."""
+    import deflate_census as DC
+    text = _texts()["genome"]
+    bam = BC.to_bam(text, member_size=20000, compress=BC.written_compress)
+    t, e = expected["genome"]
+    assert BC.sam_of(bam) == t
+    ms = BC.members(bam)
+    assert 50 < len(ms) < 400
+    c = DC.merge(DC.walk(s)[1] for _, s, _, n in ms[:3])
+    assert c["block_types"] == {2} and max(c["lit_declared"]) == 15 and max(c["dist_declared"]) == 15 and c["max_distance"] > 10000
+    g = hcbam.parse(bam)
+    assert len(g["records"]) == len(e["records"]) > 100
+    for f in SAME:
+        assert g["records"][f].tolist() == e["records"][f].tolist(), f
+    assert g["pool"].tolist() == e["pool"].tolist()
+    for k, (a, b) in enumerate(zip(g["records"], e["records"])):
+        assert hccontig.seq(g["bases"], a) == hccontig.seq(t, b), k
+        assert hccontig.qual(g["bases"], a) == hccontig.qual(t, b), k
+    header, fields = BC.split_sam(text)
+    assert g["header"] == header and g["refs"] == BC.refs_of(fields)
+    inflated = hcbam.inflate(bam)
+    off = 0
+    for k, (_, s, _, n) in enumerate(ms):
+        assert inflated["bytes"][off:off + n] == zlib.decompress(s, -15), f"member {k}"
+        off += n
 
 
 def _bam(records, refs=(("chrA", 1000), ("chrB", 50)), header=b"@HD\tVN:1.6\n", member_size=65280):
