@@ -553,4 +553,10 @@ int hc_sw_align_flat(int64_t n, const int64_t* ref_off, const int32_t* ref_len, 
     return rc;
 }
 
+// Test hook: the DP variant (1 fast, 0 generic) a batch with these maxima runs.
+int hcx_sw_dp_variant(hc_sw_params params, int32_t overhang, int32_t n1max, int32_t n2max)
+{
+    return hcsw_host::dp_variant(params, overhang, n1max, n2max);
+}
+
 }  // extern "C"

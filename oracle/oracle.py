@@ -171,6 +171,28 @@ class SWOracle(_SWLib):
             build(ref=False)
         self.lib = C.CDLL(path)
         super().__init__(self.lib.hco_sw_batch, True)
+        self.lib.hco_sw_align.argtypes = [C.c_int] * 4 + [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int,
+                                                            C.c_char_p, C.c_int, _i32p]
+        self.lib.hco_sw_align.restype = C.c_int
+
+    def score(self, s1: bytes, s2: bytes, params=(200, -150, -260, -11), overhang=9) -> int:
+        """The best end-point score of one pair's DP (hco_sw_align's *score)."""
+        sc = C.c_int32()
+        cig = C.create_string_buffer(SW_CIGAR_STRIDE * 4)
+        self.lib.hco_sw_align(*params, s1, len(s1), s2, len(s2), overhang, cig, len(cig), C.byref(sc))
+        return sc.value
+
+    def scores(self, b, params=(200, -150, -260, -11), overhang=9, shortcut=True):
+        """Per pair of a flat batch: score(), and 0 where the all-match
+        shortcut answers the pair (shortcut on)."""
+        out = np.zeros(len(b["ref_len"]), np.int32)
+        for k in range(len(out)):
+            r = b["refs"][b["ref_off"][k]:b["ref_off"][k] + b["ref_len"][k]].tobytes()
+            a = b["alts"][b["alt_off"][k]:b["alt_off"][k] + b["alt_len"][k]].tobytes()
+            if shortcut and self.lib.hco_sw_is_all_match(r, len(r), a, len(a)):
+                continue
+            out[k] = self.score(r, a, params, overhang)
+        return out
 
 
 class SWReference(_SWLib):
