@@ -7,6 +7,10 @@
 //   hc_sam_parse (kept on the device with the text, the parser's lock held
 //             until the picks are back)
 //   resolve:  contig_of per record, read back for the result
+//   scope:    (an interval call, include/hc_intervals.h) the list checked and merged on the
+//             host before any device work; asked per window and scope per record on the
+//             device (interval_kernels.hip), their counts back. The buckets then pass over
+//             the records out of scope and the picks run over the asked windows only
 //   buckets:  place, scan, scatter, sort over the concatenated positions (dense),
 //             or keys, a stable radix sort of (key, record) and the run table,
 //             sized by the records (HC_GENOME_SORTED_BUCKETS, genome_sort_kernels.hip)
@@ -35,6 +39,7 @@
 #include "genome_engine.hpp"
 #include "genome_kernels.hpp"
 #include "genome_sort_kernels.hpp"
+#include "interval_kernels.hpp"
 #include "pool.hpp"
 #include "sam_engine.hpp"
 #include "sam_kernels.hpp"
@@ -54,7 +59,8 @@ namespace {
 // No stream of its own: the kernels run on the parser's, under the parser's lock.
 Buf g_tab, g_pos, g_sort, g_win, g_picks, g_rec, g_htab{nullptr, 0, true}, g_hback{nullptr, 0, true}, g_hpicks{nullptr, 0, true},
     g_hrec{nullptr, 0, true};
-Stage g_st({&g_tab, &g_pos, &g_sort, &g_win, &g_picks, &g_rec, &g_htab, &g_hback, &g_hpicks, &g_hrec}, false);
+Buf g_iv, g_hiv{nullptr, 0, true};   // of an interval call: the merged intervals, asked and scope
+Stage g_st({&g_tab, &g_pos, &g_sort, &g_win, &g_picks, &g_rec, &g_htab, &g_hback, &g_hpicks, &g_hrec, &g_iv, &g_hiv}, false);
 
 constexpr uint32_t kKnownFlags = HC_CONTIG_F64 | HC_CONTIG_DEFAULT_MODE | HC_CONTIG_WANT_SITE_READS | HC_CONTIG_SKIP_UNPLACED |
                                  HC_GENOME_SORTED_BUCKETS;
@@ -185,6 +191,31 @@ int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records,
     a.padding = res.padding;
     a.seed = seed;
     a.pick_mode = pick_mode;
+    a.n_asked = n_windows;   // scope and asked_list stay null: every record, every window
+
+    // ---- an interval call's own workspace: [begin | end | first] go up, the rest is made on the device
+    const Merged* iv = res.with_intervals ? &res.merged : nullptr;
+    const size_t n_iv = iv ? iv->iv.size() : 0;
+    Carver ic, ihc;
+    size_t o_ib = 0, o_if = 0, iv_up = 0, o_asked = 0, o_afirst = 0, o_alist = 0, o_scope = 0, o_sfirst = 0, o_slist = 0, o_iscan = 0;
+    size_t h_ib = 0, h_counts = 0, h_alist = 0;
+    if (iv) {
+        o_ib = ic.take(sizeof(int64_t) * 2 * n_iv);
+        o_if = ic.take(sizeof(int32_t) * (size_t(n_contigs) + 1));
+        iv_up = ic.off;
+        o_asked = ic.take(sizeof(int32_t) * size_t(n_windows));
+        o_afirst = ic.take(sizeof(int64_t) * (size_t(n_windows) + 1));
+        o_alist = ic.take(sizeof(int32_t) * size_t(n_windows));
+        o_scope = ic.take(sizeof(int32_t) * size_t(std::max(dev.n_records, 1)));
+        o_sfirst = ic.take(sizeof(int64_t) * (size_t(std::max(dev.n_records, 1)) + 1));
+        o_slist = ic.take(sizeof(int32_t) * size_t(std::max(dev.n_records, 1)));
+        o_iscan = ic.take(std::max(hcsam::scan_work_bytes(n_windows), hcsam::scan_work_bytes(dev.n_records)));
+        h_ib = ihc.take(iv_up);
+        h_counts = ihc.take(sizeof(int64_t) * 2);
+        h_alist = ihc.take(sizeof(int32_t) * size_t(n_windows));
+        if (int rc = reserve(g_iv, ic.off, "interval call workspace")) return rc;
+        if (int rc = reserve(g_hiv, ihc.off, "interval call staging")) return rc;
+    }
 
     int rc = reserve(g_tab, t.blob.size(), "genome caller contig table");
     if (rc) return rc;
@@ -267,6 +298,47 @@ int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records,
         HIP_TRY(st, hipStreamSynchronize(st));
         tr.mark("resolve");
     }
+    // ---- an interval call: the asked windows and the records in scope, their counts back
+    int32_t n_scoped = dev.n_records;
+    const int32_t* scoped_list = nullptr;
+    if (iv) {
+        char* up_at = g_hiv.p + h_ib;
+        if (n_iv) {
+            std::memcpy(up_at + o_ib, iv->begin.data(), sizeof(int64_t) * n_iv);
+            std::memcpy(up_at + o_ib + sizeof(int64_t) * n_iv, iv->end.data(), sizeof(int64_t) * n_iv);
+        }
+        std::memcpy(up_at + o_if, iv->first.data(), sizeof(int32_t) * (size_t(n_contigs) + 1));
+        HIP_TRY(st, hipMemcpyAsync(g_iv.p, up_at, iv_up, hipMemcpyHostToDevice, st));
+        IntervalArgs ia{};
+        ia.g = a;
+        ia.set = IntervalSet{reinterpret_cast<const int64_t*>(g_iv.p + o_ib), reinterpret_cast<const int64_t*>(g_iv.p + o_ib) + n_iv,
+                             reinterpret_cast<const int32_t*>(g_iv.p + o_if)};
+        ia.asked = reinterpret_cast<int32_t*>(g_iv.p + o_asked);
+        ia.asked_first = reinterpret_cast<int64_t*>(g_iv.p + o_afirst);
+        ia.asked_list = reinterpret_cast<int32_t*>(g_iv.p + o_alist);
+        ia.scope = reinterpret_cast<int32_t*>(g_iv.p + o_scope);
+        ia.scope_first = reinterpret_cast<int64_t*>(g_iv.p + o_sfirst);
+        ia.scoped_list = reinterpret_cast<int32_t*>(g_iv.p + o_slist);
+        ia.scan_work = reinterpret_cast<int64_t*>(g_iv.p + o_iscan);
+        HIP_TRY(st, launch_interval_ask(ia, st));
+        HIP_TRY(st, launch_interval_scope(ia, st));
+        HIP_TRY(st, hipMemcpyAsync(g_hiv.p + h_counts, ia.asked_first + n_windows, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(st, hipMemcpyAsync(g_hiv.p + h_counts + sizeof(int64_t), ia.scope_first + dev.n_records, sizeof(int64_t),
+                                   hipMemcpyDeviceToHost, st));
+        HIP_TRY(st, hipStreamSynchronize(st));
+        int64_t counts[2];
+        std::memcpy(counts, g_hiv.p + h_counts, sizeof(counts));
+        if (counts[0] < 0 || counts[0] > n_windows || counts[1] < 0 || counts[1] > dev.n_records)
+            return fail(HC_PHMM_EHIP, "interval call: asked or scoped count out of its bound");
+        a.n_asked = int32_t(counts[0]);
+        a.asked_list = ia.asked_list;
+        a.scope = ia.scope;
+        n_scoped = int32_t(counts[1]);
+        scoped_list = ia.scoped_list;
+        if (a.n_asked)   // complete at the sync behind the pick counts
+            HIP_TRY(st, hipMemcpyAsync(g_hiv.p + h_alist, ia.asked_list, sizeof(int32_t) * size_t(a.n_asked), hipMemcpyDeviceToHost, st));
+        tr.mark("scope");
+    }
     GenomeSortArgs s{};
     if (!sorted) {
         HIP_TRY(st, hipMemsetAsync(g_pos.p, 0, zero_bytes, st));
@@ -277,6 +349,8 @@ int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records,
         HIP_TRY(st, launch_sort(a, st));
     } else {
         s.g = a;
+        s.n = n_scoped;   // a plain call: every record
+        s.scoped = scoped_list;
         for (int k = 0; k < 2; ++k) {
             s.key[k] = reinterpret_cast<int64_t*>(g_sort.p + o_key[k]);
             s.index[k] = reinterpret_cast<int32_t*>(g_sort.p + o_index[k]);
@@ -295,6 +369,7 @@ int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records,
         tr.mark("buckets");
     }
     // ---- the picks: their counts first, so that the lists take what they need and no more
+    if (iv) HIP_TRY(st, hipMemsetAsync(a.n_picked, 0, sizeof(int32_t) * size_t(n_windows), st));   // a window not asked picks nothing
     HIP_TRY(st, sorted ? launch_sorted_pick_count(s, st) : launch_pick_count(a, st));
     HIP_TRY(st, hcsam::launch_scan(a.n_picked, n_windows, win_first, scan_work, st));
     HIP_TRY(st, hipMemcpyAsync(g_hback.p + h_err, a.err, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -307,6 +382,13 @@ int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records,
     for (int32_t c : res.contig_of) {
         if (c < -1 || c >= n_contigs) return fail(HC_PHMM_EHIP, "genome caller: a record's contig is out of its bound");
         if (c >= 0) ++res.n_records[size_t(c)];
+    }
+    if (iv) {
+        const int32_t* ha = reinterpret_cast<const int32_t*>(g_hiv.p + h_alist);
+        res.asked.assign(ha, ha + a.n_asked);
+        for (size_t k = 0; k < res.asked.size(); ++k)
+            if (res.asked[k] < 0 || res.asked[k] >= n_windows || (k && res.asked[k] <= res.asked[k - 1]))
+                return fail(HC_PHMM_EHIP, "interval call: the asked windows do not ascend inside their bound");
     }
     unsigned long long err = 0;
     std::memcpy(&err, g_hback.p + h_err, sizeof(err));
@@ -358,6 +440,11 @@ int tile(Front& front, const hcsam::Resident& dev, const hc_sam_record* records,
     tr.count("sorted", sorted ? 1 : 0);
     tr.count("sort_passes", sorted ? s.passes : 0);
     tr.count("tile_bytes", int64_t(rec_bytes + pc.off + wc.off));   // asked of the record, position / sort and window workspaces
+    if (iv) {
+        tr.count("intervals", int64_t(n_iv));
+        tr.count("asked", a.n_asked);
+        tr.count("scoped", n_scoped);
+    }
     const int32_t* hp = reinterpret_cast<const int32_t*>(g_hpicks.p);
     res.picked.assign(hp, hp + total);
     for (int32_t k : res.picked)
@@ -430,7 +517,8 @@ int run(Front& front, const hc_genome_contig* contigs, int32_t n_contigs, const 
     std::vector<int32_t> sent;   // the windows with reads, of all contigs
     for (int32_t w = 0; w < n_windows; ++w)
         if (res.win_first[size_t(w) + 1] > res.win_first[size_t(w)]) sent.push_back(w);
-    res.status.assign(size_t(n_windows), HC_CALL_NO_READS);
+    res.status.assign(size_t(n_windows), res.with_intervals ? HC_CALL_NOT_ASKED : HC_CALL_NO_READS);
+    for (int32_t w : res.asked) res.status[size_t(w)] = HC_CALL_NO_READS;
     res.asm_status.assign(size_t(n_windows), HC_ASM_NO_HAPLOTYPES);
     res.kmer_size.assign(size_t(n_windows), 0);
     res.n_haps.assign(size_t(n_windows), 0);
@@ -497,8 +585,17 @@ int run(Front& front, const hc_genome_contig* contigs, int32_t n_contigs, const 
               "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype Quality\">\n"
               "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
               "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tNA12878\n";
-    for (const hc_gt_call_site& s : res.sites)
-        if (s.status == HC_GT_SITE_EMITTED) print_site(res.vcf, res.names[size_t(res.win_contig[size_t(s.region)])], s);
+    // of an interval call: the sites that begin inside a merged interval of their contig
+    if (!res.with_intervals) {
+        for (const hc_gt_call_site& s : res.sites)
+            if (s.status == HC_GT_SITE_EMITTED) print_site(res.vcf, res.names[size_t(res.win_contig[size_t(s.region)])], s);
+    } else {
+        const IntervalSet set{res.merged.begin.data(), res.merged.end.data(), res.merged.first.data()};
+        for (const hc_gt_call_site& s : res.sites) {
+            const int32_t c = res.win_contig[size_t(s.region)];
+            if (s.status == HC_GT_SITE_EMITTED && interval_meets(set, c, s.begin, s.begin + 1)) print_site(res.vcf, res.names[size_t(c)], s);
+        }
+    }
     tr.mark("vcf");
     tr.value("contigs", double(n_contigs));
     tr.value("windows", double(n_windows));
@@ -545,7 +642,8 @@ struct SamFront final : Front {
 }  // namespace
 
 int hcgenome::genome_call(Front& front, const hc_genome_contig* contigs, int32_t n_contigs, int32_t region_size,
-                          int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags_in, hc_genome_result** out)
+                          int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags_in, hc_genome_result** out,
+                          const Asking* ask)
 {
     std::lock_guard<std::mutex> lk(g_st.mu);
     return call_frame(out, nullptr, [&](hc_genome_result& res) -> int {
@@ -573,6 +671,15 @@ int hcgenome::genome_call(Front& front, const hc_genome_contig* contigs, int32_t
             res.win_off.push_back(res.win_off.back() + (contigs[k].ref_len + region_size - 1) / region_size);
             if (res.win_off.back() > 0x7fffffffLL) return fail(HC_PHMM_EINVAL, "more than 2147483647 windows");
         }
+        if (ask) {
+            if (!ask->intervals) return fail(HC_PHMM_EINVAL, "null intervals");
+            if (ask->n < 1) return fail(HC_PHMM_EINVAL, "n_intervals below 1");
+            std::string why;
+            const int64_t bad = interval_check(ask->intervals, ask->n, res.ref_len.data(), n_contigs, why);
+            if (bad >= 0) return fail(HC_PHMM_EINVAL, "interval " + std::to_string(bad) + ": " + why);
+            interval_merge(ask->intervals, ask->n, n_contigs, res.merged);
+            res.with_intervals = true;
+        }
         Table t;
         if (int rc = build_table(contigs, n_contigs, res, t)) return rc;
         return run(front, contigs, n_contigs, t, seed, pick_mode, flags, res);
@@ -585,6 +692,27 @@ extern "C" int hc_genome_call(const uint8_t* sam, int64_t sam_len, const hc_geno
 {
     SamFront front(sam, sam_len);
     return genome_call(front, contigs, n_contigs, region_size, padding_size, seed, pick_mode, flags, out);
+}
+
+extern "C" int hc_genome_call_intervals(const uint8_t* sam, int64_t sam_len, const hc_genome_contig* contigs, int32_t n_contigs,
+                                        const hc_interval* intervals, int32_t n_intervals, int32_t region_size,
+                                        int32_t padding_size, uint64_t seed, int32_t pick_mode, uint32_t flags,
+                                        hc_genome_result** out)
+{
+    SamFront front(sam, sam_len);
+    const Asking ask{intervals, n_intervals};
+    return genome_call(front, contigs, n_contigs, region_size, padding_size, seed, pick_mode, flags, out, &ask);
+}
+
+extern "C" int hc_genome_result_intervals(const hc_genome_result* res, const hc_interval** merged, int32_t* n_merged,
+                                          const int32_t** asked, int32_t* n_asked)
+{
+    if (!res) return fail(HC_PHMM_EINVAL, "null result");
+    if (merged) *merged = res->merged.iv.data();
+    if (n_merged) *n_merged = int32_t(res->merged.iv.size());
+    if (asked) *asked = res->asked.data();
+    if (n_asked) *n_asked = int32_t(res->asked.size());
+    return HC_PHMM_OK;
 }
 
 extern "C" int hc_genome_result_vcf(const hc_genome_result* res, const char** text, int64_t* length, int32_t* n_windows,

@@ -13,7 +13,9 @@
 #include <vector>
 
 #include "../../include/hc_genome.h"
+#include "../../include/hc_intervals.h"
 #include "genome_kernels.hpp"
+#include "interval_host.hpp"
 #include "sam_engine.hpp"
 #include "stage_host.hpp"
 
@@ -33,6 +35,11 @@ struct hc_genome_result {
     std::vector<std::vector<int32_t>> reads; // per window: the surviving reads, record indices
     std::string vcf;
     std::vector<uint8_t> bases;              // of a BAM call: what the records' `line` offsets point into
+    bool with_intervals = false;             // of an interval call (hc_intervals.h)
+    hcgenome::Merged merged;                 //   its merged intervals
+    std::vector<int32_t> asked;              //   the asked windows, ascending
+    int32_t idx_chunks = 0, idx_members = 0; //   of an indexed BAM call: chunks after merging, members read,
+    int64_t idx_bytes_up = 0, idx_records = 0;   // compressed bytes uploaded, records framed
     ~hc_genome_result();
 };
 
@@ -71,7 +78,14 @@ struct Front {
     virtual std::string rname(const hc_sam_record& r, size_t k) const = 0;
 };
 
+// The intervals of an interval call, as the caller gave them (checked by genome_call).
+struct Asking {
+    const hc_interval* intervals;
+    int32_t n;
+};
+
+// `ask` null: the plain call, every window of every contig.
 int genome_call(Front& front, const hc_genome_contig* contigs, int32_t n_contigs, int32_t region_size, int32_t padding_size,
-                uint64_t seed, int32_t pick_mode, uint32_t flags, hc_genome_result** out);
+                uint64_t seed, int32_t pick_mode, uint32_t flags, hc_genome_result** out, const Asking* ask = nullptr);
 
 }  // namespace hcgenome

@@ -13,7 +13,10 @@
 //   (scan of the counts: sam_scan_kernel)
 //   genome_scatter_kernel, genome_sort_kernel
 //                          as the contig caller's, over the concatenated positions.
-//   genome_pick_kernel     one wave per genome-wide window: its contig by binary
+//                          A record out of an interval call's scope (scope[k] == 0)
+//                          is passed over by place and scatter: no count, no error.
+//   genome_pick_kernel     one wave per genome-wide window, or per asked window of
+//                          an interval call's list: its contig by binary
 //                          search over the windows' exclusive sums (wave-uniform),
 //                          its padded interval from the contig-local window index,
 //                          begun at the contig's position 0 and cut at its end, so
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void genome_resolve_kernel(Gen
 __global__ __launch_bounds__(256) void genome_place_kernel(GenomeArgs a)
 {
     const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (k >= a.n_records) return;
+    if (k >= a.n_records || (a.scope && !a.scope[k])) return;
     const hc_sam_record r = a.records[k];
     const int32_t c = a.contig_of[k];
     const unsigned long long line = static_cast<unsigned long long>(a.line_no[k]);
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(256) void genome_place_kernel(GenomeArgs a)
 __global__ __launch_bounds__(256) void genome_scatter_kernel(GenomeArgs a)
 {
     const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (k >= a.n_records) return;
+    if (k >= a.n_records || (a.scope && !a.scope[k])) return;
     const hc_sam_record r = a.records[k];
     const int32_t c = a.contig_of[k];
     if (!genome_placed(c, r.pos, a.ref_len)) return;
@@ -94,8 +97,9 @@ template <bool kWrite>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void genome_pick_kernel(GenomeArgs a)
 {
     const int lane = int(threadIdx.x) & 63;
-    const int64_t w = int64_t(blockIdx.x) * kWavesPerBlock + (int(threadIdx.x) >> 6);
-    if (w >= a.n_windows) return;   // wave-uniform
+    const int64_t i = int64_t(blockIdx.x) * kWavesPerBlock + (int(threadIdx.x) >> 6);
+    if (i >= a.n_asked) return;   // wave-uniform
+    const int64_t w = genome_pick_window(a, i);
     const int32_t c = genome_contig_of_window(a.win_off, a.n_contigs, w);
     const int64_t lw = w - a.win_off[c];   // the contig's own window index
     const int64_t len = a.ref_len[c];
@@ -150,14 +154,16 @@ hipError_t launch_sort(const GenomeArgs& a, hipStream_t st)
 
 hipError_t launch_pick_count(const GenomeArgs& a, hipStream_t st)
 {
-    hipLaunchKernelGGL(genome_pick_kernel<false>, dim3(blocks_of(a.n_windows, kWavesPerBlock)), dim3(64 * kWavesPerBlock), 0,
+    if (a.n_asked <= 0) return hipSuccess;
+    hipLaunchKernelGGL(genome_pick_kernel<false>, dim3(blocks_of(a.n_asked, kWavesPerBlock)), dim3(64 * kWavesPerBlock), 0,
                        st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_pick_write(const GenomeArgs& a, hipStream_t st)
 {
-    hipLaunchKernelGGL(genome_pick_kernel<true>, dim3(blocks_of(a.n_windows, kWavesPerBlock)), dim3(64 * kWavesPerBlock), 0,
+    if (a.n_asked <= 0) return hipSuccess;
+    hipLaunchKernelGGL(genome_pick_kernel<true>, dim3(blocks_of(a.n_asked, kWavesPerBlock)), dim3(64 * kWavesPerBlock), 0,
                        st, a);
     return hipGetLastError();
 }

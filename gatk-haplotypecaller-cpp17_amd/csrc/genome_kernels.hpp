@@ -45,7 +45,14 @@ struct GenomeArgs {
     const int64_t* win_first;  // its exclusive scan
     int32_t* picked;           // per pick: record indices, window-major, ascending position
     unsigned long long* err;
+    // Of an interval call (interval_kernels.hpp); null in a plain call.
+    const int32_t* scope;      // per record: 0 keeps it out of the buckets and raises no error. Null: every record.
+    const int32_t* asked_list; // the windows that pick, ascending; the others' n_picked is zeroed beforehand. Null: every window.
+    int32_t n_asked;           // their number; n_windows without a list
 };
+
+// The window of pick wave i (0 <= i < n_asked).
+__host__ __device__ inline int64_t genome_pick_window(const GenomeArgs& a, int64_t i) { return a.asked_list ? a.asked_list[i] : i; }
 
 hipError_t launch_resolve(const GenomeArgs& a, hipStream_t st);
 hipError_t launch_place(const GenomeArgs& a, hipStream_t st);

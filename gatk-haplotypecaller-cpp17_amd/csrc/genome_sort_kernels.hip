@@ -3,7 +3,8 @@
 // stores; no global atomic decides where an element goes, so two runs give the
 // same bytes. The rules are genome_sort_body.hpp's.
 //
-//   genome_sort_keys_kernel     one lane per record: genome_place_kernel's
+//   genome_sort_keys_kernel     one lane per record, or per record of an interval
+//                               call's scoped list: genome_place_kernel's
 //                               placement and defect tests and its two
 //                               atomicMins; the key is off[contig] + POS - 1, or
 //                               total_len for an unplaced read, the payload the
@@ -26,7 +27,8 @@
 //   genome_sort_runs_kernel     one lane per sorted element: a head stores its
 //                               run's key and first element; the last placed
 //                               read closes the table.
-//   genome_sorted_pick_kernel   one wave per genome-wide window, its contig and
+//   genome_sorted_pick_kernel   one wave per genome-wide window, or per asked window
+//                               of an interval call's list, its contig and
 //                               padded interval as genome_pick_kernel's; two
 //                               wave-uniform lower bounds over the run keys give
 //                               its runs (the second over no more runs than the
@@ -39,10 +41,12 @@
 
 namespace hcgenome {
 
-__global__ __launch_bounds__(256) void genome_sort_keys_kernel(GenomeArgs a, int64_t* key, int32_t* index)
+__global__ __launch_bounds__(256) void genome_sort_keys_kernel(GenomeArgs a, const int32_t* scoped, int32_t n, int64_t* key,
+                                                               int32_t* index)
 {
-    const int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (k >= a.n_records) return;
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t k = scoped ? scoped[i] : i;   // below n_records: the list holds record indices
     const hc_sam_record r = a.records[k];
     const int32_t c = a.contig_of[k];
     const unsigned long long line = static_cast<unsigned long long>(a.line_no[k]);
@@ -54,8 +58,8 @@ __global__ __launch_bounds__(256) void genome_sort_keys_kernel(GenomeArgs a, int
         if (!filtered && r.defect) atomicMin(a.err, line * 16ull + kErrDefect);
         at = a.off[c] + int64_t(r.pos - 1u);
     }
-    key[k] = at;
-    index[k] = int32_t(k);
+    key[i] = at;
+    index[i] = int32_t(k);
 }
 
 __global__ __launch_bounds__(kSortBlock) void genome_sort_hist_kernel(const int64_t* key, int32_t n, int pass, int32_t* hist,
@@ -144,8 +148,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void genome_sorted_pick_kernel
 {
     const GenomeArgs& a = s.g;
     const int lane = int(threadIdx.x) & 63;
-    const int64_t w = int64_t(blockIdx.x) * kWavesPerBlock + (int(threadIdx.x) >> 6);
-    if (w >= a.n_windows) return;   // wave-uniform, as is everything below that is not indexed by `lane`
+    const int64_t i = int64_t(blockIdx.x) * kWavesPerBlock + (int(threadIdx.x) >> 6);
+    if (i >= a.n_asked) return;   // wave-uniform, as is everything below that is not indexed by `lane`
+    const int64_t w = genome_pick_window(a, i);
     const int32_t c = genome_contig_of_window(a.win_off, a.n_contigs, w);
     const int64_t lw = w - a.win_off[c];   // the contig's own window index
     const int64_t len = a.ref_len[c];
@@ -154,7 +159,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void genome_sorted_pick_kernel
     int64_t end = origin + a.region + a.padding;
     if (end > len) end = len;   // positions at and past the contig's end are another contig's
     const int64_t off = a.off[c];
-    const int64_t n_runs = s.run_of[a.n_records];
+    const int64_t n_runs = s.run_of[s.n];
     const int64_t r0 = sort_lower_bound(s.run_pos, n_runs, off + begin);
     // the run keys are distinct and ascending, so run r0 + j lies at or behind begin + j: the second search is short
     const int64_t most = n_runs - r0 < end - begin ? n_runs - r0 : end - begin;
@@ -175,7 +180,7 @@ static unsigned blocks_of(int64_t n, int per) { return unsigned((n + per - 1) / 
 
 hipError_t launch_sorted_buckets(GenomeSortArgs& a, hipStream_t st)
 {
-    const int32_t n = a.g.n_records;
+    const int32_t n = a.n;
     const int32_t n_tiles = int32_t(sort_tiles(n));
     const int last = a.passes & 1;
     a.keys = a.key[last];
@@ -184,7 +189,8 @@ hipError_t launch_sorted_buckets(GenomeSortArgs& a, hipStream_t st)
     int64_t* run_of = a.key[last ^ 1];
     a.run_of = run_of;
     if (n > 0) {
-        hipLaunchKernelGGL(genome_sort_keys_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, a.g, a.key[0], a.index[0]);
+        hipLaunchKernelGGL(genome_sort_keys_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, a.g, a.scoped, n, a.key[0],
+                           a.index[0]);
         for (int pass = 0; pass < a.passes; ++pass) {
             const int in = pass & 1;
             hipLaunchKernelGGL(genome_sort_hist_kernel, dim3(unsigned(n_tiles)), dim3(kSortBlock), 0, st, a.key[in], n, pass, a.hist,
@@ -205,14 +211,16 @@ hipError_t launch_sorted_buckets(GenomeSortArgs& a, hipStream_t st)
 
 hipError_t launch_sorted_pick_count(const GenomeSortArgs& a, hipStream_t st)
 {
-    hipLaunchKernelGGL(genome_sorted_pick_kernel<false>, dim3(blocks_of(a.g.n_windows, kWavesPerBlock)), dim3(64 * kWavesPerBlock),
+    if (a.g.n_asked <= 0) return hipSuccess;
+    hipLaunchKernelGGL(genome_sorted_pick_kernel<false>, dim3(blocks_of(a.g.n_asked, kWavesPerBlock)), dim3(64 * kWavesPerBlock),
                        0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_sorted_pick_write(const GenomeSortArgs& a, hipStream_t st)
 {
-    hipLaunchKernelGGL(genome_sorted_pick_kernel<true>, dim3(blocks_of(a.g.n_windows, kWavesPerBlock)), dim3(64 * kWavesPerBlock),
+    if (a.g.n_asked <= 0) return hipSuccess;
+    hipLaunchKernelGGL(genome_sorted_pick_kernel<true>, dim3(blocks_of(a.g.n_asked, kWavesPerBlock)), dim3(64 * kWavesPerBlock),
                        0, st, a);
     return hipGetLastError();
 }

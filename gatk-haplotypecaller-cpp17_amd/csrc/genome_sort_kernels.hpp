@@ -12,11 +12,15 @@
 namespace hcgenome {
 
 // `g` is the dense path's record with count, first, cursor and bucket unused.
-// n = g.n_records, tiles = sort_tiles(n). key[0] is the buffer the keys are made
+// n elements are sorted: every record (scoped null, n = g.n_records), or the
+// records of an interval call's scoped list, which ascends, so that the reads of
+// a position stay in file order. tiles = sort_tiles(n). key[0] is the buffer the keys are made
 // in; the sort leaves its result in key[passes & 1] / index[passes & 1], and the
 // other pair is free from then on: its keys hold run_of, its indices the head flags.
 struct GenomeSortArgs {
     GenomeArgs g;
+    int32_t n;               // the elements
+    const int32_t* scoped;   // n record indices, ascending, or null
     int64_t* key[2];      // n + 1 each
     int32_t* index[2];    // n each
     int32_t* hist;        // kSortDigits * tiles, digit-major

@@ -66,17 +66,38 @@ stage_host::Stage& hcsam::parser_stage() { return g_st; }
 
 int hcsam::upload(const uint8_t* bytes, int64_t len, size_t room, const uint8_t*& on_device)
 {
-    const size_t stage = std::min(stage_bytes(), size_t(len));
+    const Piece whole{bytes, len};
+    return upload_pieces(&whole, 1, len, room, on_device);
+}
+
+int hcsam::upload_pieces(const Piece* pieces, size_t n_pieces, int64_t total, size_t room, const uint8_t*& on_device)
+{
+    const size_t stage = std::min(stage_bytes(), size_t(total));
     int rc = reserve(g_text, room, "SAM text on the device");
     if (rc) return rc;
     rc = reserve(g_stage, stage, "SAM text staging");
     if (rc) return rc;
-    for (int64_t off = 0; off < len; off += int64_t(stage)) {
-        const size_t n = size_t(std::min<int64_t>(int64_t(stage), len - off));
-        std::memcpy(g_stage.p, bytes + off, n);
-        HIP_TRY(g_st.stream, hipMemcpyAsync(g_text.p + off, g_stage.p, n, hipMemcpyHostToDevice, g_st.stream));
+    int64_t up = 0;    // bytes on the device
+    size_t fill = 0;   // bytes in the block
+    const auto flush = [&]() -> int {
+        if (!fill) return HC_PHMM_OK;
+        HIP_TRY(g_st.stream, hipMemcpyAsync(g_text.p + up, g_stage.p, fill, hipMemcpyHostToDevice, g_st.stream));
         HIP_TRY(g_st.stream, hipStreamSynchronize(g_st.stream));   // the block is reused by the next piece
+        up += int64_t(fill);
+        fill = 0;
+        return HC_PHMM_OK;
+    };
+    for (size_t k = 0; k < n_pieces && stage; ++k) {
+        for (int64_t off = 0; off < pieces[k].len && up + int64_t(fill) < total;) {   // never past `total` <= room
+            const size_t n = size_t(std::min<int64_t>({int64_t(stage - fill), pieces[k].len - off, total - up - int64_t(fill)}));
+            std::memcpy(g_stage.p + fill, pieces[k].bytes + off, n);
+            fill += n;
+            off += int64_t(n);
+            if (fill == stage)
+                if (int e = flush()) return e;
+        }
     }
+    if (int e = flush()) return e;
     on_device = reinterpret_cast<const uint8_t*>(g_text.p);
     return HC_PHMM_OK;
 }

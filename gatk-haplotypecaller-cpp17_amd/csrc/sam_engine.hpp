@@ -42,5 +42,12 @@ stage_host::Stage& parser_stage();
 // through the pinned staging block of HC_SAM_STAGE_BYTES, piece after piece, into
 // the parser's text buffer of at least `room` >= len bytes.
 int upload(const uint8_t* bytes, int64_t len, size_t room, const uint8_t*& on_device);
+// The same for stretches of host bytes that lie apart: they are packed one behind
+// the other in the staging block itself, `total` bytes in all, with no copy in between.
+struct Piece {
+    const uint8_t* bytes;
+    int64_t len;
+};
+int upload_pieces(const Piece* pieces, size_t n_pieces, int64_t total, size_t room, const uint8_t*& on_device);
 
 }  // namespace hcsam

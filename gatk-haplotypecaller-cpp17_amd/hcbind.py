@@ -1,5 +1,5 @@
 """What the Python mirrors of the C headers share (hcphmm, hcsw, hcgt, hcregion,
-hcasm, hcprep, hccall, hccontig, hcgenome, hcbam): the pointer types, the base of their error
+hcasm, hcprep, hccall, hccontig, hcgenome, hcbam, hcintervals): the pointer types, the base of their error
 classes, the header / binding symbol lists of the export tests, the return code
 check and the conversion of hc_gt_call_site records to dicts.
 """
