@@ -164,11 +164,15 @@ void paths_from_graph(const uint8_t* source_kmer, int32_t kmer_size, const hc_as
         },
         [&](int32_t e) { prefix.push_back(prefix.back() + score[size_t(e)]); }, [&] { prefix.pop_back(); });
 
-    // std::sort by score descending, made stable; the first HC_ASM_MAX_HAPS stay
+    // std::sort by score descending over the paths in discovery order, as
+    // graph_wrapper.hpp:220 sorts its haplotypes; the first HC_ASM_MAX_HAPS stay.
+    // Not a stable sort: where scores are equal, std::sort's permutation is a
+    // function of the comparison results alone, so with the same C++ library it
+    // is the reference's, element type regardless.
     std::vector<int32_t> order(path_score.size());
     std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](int32_t a, int32_t b) { return path_score[size_t(a)] > path_score[size_t(b)]; });
+    std::sort(order.begin(), order.end(),
+              [&](int32_t a, int32_t b) { return path_score[size_t(a)] > path_score[size_t(b)]; });
     if (order.size() > size_t(HC_ASM_MAX_HAPS)) order.resize(size_t(HC_ASM_MAX_HAPS));
     std::vector<int32_t> rank(path_score.size(), -1);
     for (size_t r = 0; r < order.size(); ++r) rank[size_t(order[r])] = int32_t(r);

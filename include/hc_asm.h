@@ -19,8 +19,12 @@
  *                is_ref || count >= 2 || out_degree(source) == 1.
  *   haplotypes   every source -> sink path depth first in out-edge order, scored
  *                by sum of log10(count / sum of on-path sibling counts), sorted
- *                by score descending with a STABLE sort (equal scores keep
- *                discovery order), the first HC_ASM_MAX_HAPS kept.
+ *                by score descending with std::sort and the reference's comparator
+ *                over the paths in discovery order, the first HC_ASM_MAX_HAPS
+ *                kept. Among equal scores that is the reference's order (and its
+ *                choice at the cut) wherever both are built with the same C++
+ *                library: discovery order for up to 16 paths with libstdc++,
+ *                introsort's permutation beyond.
  *
  * The graph is built on the device (one workgroup per region), the paths are
  * enumerated and scored on the host (glibc log10). Deviation from the reference:

@@ -484,3 +484,65 @@ class ChainReference:
 
 def chain_reference_available() -> bool:
     return os.path.exists(REF_CHAIN_SO)
+
+
+# --------------------------------------------------------------------------
+# The reference's assembler compiled in place (oracle/_ref/libref_asm.so,
+# oracle/ref_asm_driver.cpp): Assembler::assemble over GraphWrapper, with
+# oracle/boost_standin/boost/graph/ for the container and the DFS.
+REF_ASM_SO = os.path.join(HERE, "_ref", "libref_asm.so")
+
+
+class AsmReference:
+    """hcr_asm. assemble() returns the record the asm fixture keeps: status,
+    kmer_size, attempts (the codes of include/hc_asm.h), unique (the unique
+    k-mer count of every attempt that built a graph), n_paths, haps [(bases,
+    score)] in the reference's order, source, sink and edges [(from, to, last
+    byte, count, is_ref, is_on_path, creation index)] of the accepted graph.
+    Raises ReferenceThrew where the reference threw."""
+
+    SMALL = -2
+
+    def __init__(self, path: str = REF_ASM_SO):
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self.lib = C.CDLL(path)
+        self.lib.hcr_asm.argtypes = [C.c_char_p, C.c_long, C.c_long, _i64p, _i32p, _u8p, _u8p, _u8p, C.c_long]
+        self.lib.hcr_asm.restype = C.c_long
+
+    def assemble(self, reads, ref: bytes):
+        lens = np.array([len(b) for b, _ in reads], np.int32)
+        offs = np.zeros(len(reads), np.int64)
+        if len(reads):
+            offs[1:] = np.cumsum(lens[:-1])
+        bases = np.frombuffer(b"".join(b for b, _ in reads) + b"\0", np.uint8).copy()
+        quals = np.frombuffer(b"".join(q for _, q in reads) + b"\0", np.uint8).copy()
+        cap = 1 << 20
+        while True:
+            buf = np.zeros(cap, np.uint8)
+            n = self.lib.hcr_asm(ref, len(ref), len(reads), _ptr(offs if len(reads) else np.zeros(1, np.int64), _i64p),
+                                 _ptr(lens if len(reads) else np.zeros(1, np.int32), _i32p), _ptr(bases, _u8p),
+                                 _ptr(quals, _u8p), _ptr(buf, _u8p), cap)
+            if n == self.SMALL:
+                cap *= 8
+                continue
+            break
+        b = _Blob(buf[:n].tobytes())
+        if b.i64():
+            raise ReferenceThrew()
+        haps = []
+        for _ in range(b.i64()):
+            bases_ = b.bytes_()
+            haps.append((bases_, float(b.f64s(1)[0])))
+        att = b.i64s(18).reshape(9, 2)
+        out = dict(attempts=att[:, 0].tolist(), unique=att[:, 1].tolist(), haps=haps, kmer_size=b.i64(), n_paths=b.i64(),
+                   source=b.i64(), sink=b.i64())
+        ne = b.i64()
+        out["edges"] = [tuple(row) for row in b.i64s(7 * ne).reshape(ne, 7).tolist()]
+        out["status"] = 0 if haps else 1   # HC_ASM_OK / HC_ASM_NO_HAPLOTYPES
+        b.end()
+        return out
+
+
+def asm_reference_available() -> bool:
+    return os.path.exists(REF_ASM_SO)

@@ -7,8 +7,9 @@
 // genotyper/genotyper.hpp. No reference source is copied into this repository.
 // The three Boost.Serialization headers those files include (and use nothing
 // of) are answered by oracle/boost_standin/, which holds standard includes only.
-// assembler/graph_wrapper.hpp needs Boost.Graph for real, so the assembler and
-// haplotypecaller.hpp (which includes it) are not compiled here.
+// assembler/graph_wrapper.hpp needs Boost.Graph for real: the assembler is
+// compiled by ref_asm_driver.cpp, over a stand-in container of its own, and
+// haplotypecaller.hpp (which includes it) is not compiled at all.
 //
 // What this file restates, because it lies in haplotypecaller.hpp or inside one
 // reference function and cannot be called: the ORCHESTRATION only, marked

@@ -4,11 +4,18 @@ A literal transliteration of assembler/graph_wrapper.hpp and
 assembler/assembler.hpp into plain Python: dictionaries for the two k-mer maps,
 lists for the adjacency lists (out-edge order = creation order, as boost's vecS
 keeps it), one edge record per add_edge. It shares no code with the library.
-The reference itself needs Boost.Graph and cannot be compiled next to this
-suite, so this file is what pins parity (DESIGN.md §19 says so).
+The reference itself is compiled next to this suite (oracle/ref_asm_driver.cpp,
+over a stand-in for Boost.Graph) and tests/test_asm_ref_pins.py holds this file
+to it, live and through tests/golden/asm_golden.npz.
 
-Two things are stated here because the reference leaves them open:
-  * the sort of get_haplotypes is stable (equal scores keep discovery order);
+Two things differ from the reference here, on purpose:
+  * the sort of get_haplotypes is stable (equal scores keep discovery order).
+    The reference's std::sort is not: among equal scores its order, and at the
+    cut of 128 its choice, are what the C++ library's introsort makes of the
+    comparison results. The library follows the reference there
+    (csrc/asm_paths.cpp) and is pinned to the fixture exactly; this file is
+    compared with the reference up to the order within runs of equal score
+    bits, and up to which members of such a run stay where it straddles the cut;
   * more than MAX_PATHS paths in an attempt end the region as TOO_COMPLEX
     (the reference enumerates without bound).
 """
@@ -233,7 +240,8 @@ class GraphWrapper:
                 seq.append(self.kmer[v][-1])
                 score += self.edge(u, v).score
             haps.append((bytes(seq), score))
-        haps.sort(key=lambda h: -h[1])   # stable: the tie rule
+        haps.sort(key=lambda h: -h[1])   # stable: this file's tie rule, not the reference's (see the docstring)
+        self.sorted_haps = haps          # before the cut: what a run of equal scores at the cut is compared against
         return haps[:DEFAULT_NUM_PATHS]
 
     def reduced_graph(self):

@@ -7,6 +7,7 @@
 //                       (csrc/asm_graph_body.hpp) compiled for one host thread, with the
 //                       ballot arithmetic of asm_segments_kernel emulated lane by lane,
 //                       then the paths. What the device computes, bounds checked.
+//   emulslot <in> <out> the same with one workspace slice for all the regions, in order
 //
 // Files are text, bytes in hex:
 //   graph in:  k source_kmer source sink n_edges, then n_edges x "from to count seq base is_ref"
@@ -183,82 +184,125 @@ static void segments(const AsmSeq& s, const uint8_t* bases, const uint8_t* quals
     }
 }
 
-static int mode_emul(const char* in, const char* outp)
+// One region's input as the device sees it: the window then the reads in one pool.
+struct EmulRegion {
+    std::vector<uint8_t> bases, quals;
+    std::vector<AsmSeq> seqs;
+    AsmRegion rg{};
+};
+
+// A workgroup's slice of the workspace (AsmSlot), sized for a region.
+struct EmulSlot {
+    std::vector<uint32_t> id, h_rep, h_min;
+    std::vector<int32_t> vert_of;
+    std::vector<uint8_t> dup;
+    std::vector<AsmVertex> vs;
+    std::vector<AsmEdge> es;
+    void grow(const AsmRegion& rg)
+    {
+        const size_t n = size_t(rg.n_bases), h = size_t(rg.hash_size), c = size_t(rg.cap);
+        if (id.size() < n) id.resize(n), vert_of.resize(n), dup.resize(n);
+        if (h_rep.size() < h) h_rep.resize(h), h_min.resize(h);
+        if (vs.size() < c) vs.resize(c), es.resize(c);
+    }
+    AsmSlot slot() { return AsmSlot{id.data(), vert_of.data(), dup.data(), h_rep.data(), h_min.data(), vs.data(), es.data()}; }
+};
+
+static bool read_region(std::istream& is, EmulRegion& x)
+{
+    std::string ref_hex;
+    int n_reads;
+    is >> ref_hex >> n_reads;
+    x.bases = unhex(ref_hex);
+    const int32_t ref_len = int32_t(x.bases.size());
+    x.quals.assign(x.bases.size(), 0);
+    x.seqs.assign(1, AsmSeq{0, ref_len, 0, 1, 0});
+    int64_t cap = std::max(0, ref_len - (kFirstK - 1));
+    for (int j = 0; j < n_reads; ++j) {
+        std::string bh, qh;
+        is >> bh >> qh;
+        const std::vector<uint8_t> b = unhex(bh), q = unhex(qh);
+        if (b.size() != q.size()) return false;
+        x.seqs.push_back(AsmSeq{int64_t(x.bases.size()), int32_t(b.size()), int32_t(x.bases.size()), 0, 0});
+        x.bases.insert(x.bases.end(), b.begin(), b.end());
+        x.quals.insert(x.quals.end(), q.begin(), q.end());
+        cap += std::max<int64_t>(0, int64_t(b.size()) - (kFirstK - 1));
+    }
+    if (!is) return false;
+    x.rg = AsmRegion{0, ref_len, int32_t(x.bases.size()), int32_t(std::max<int64_t>(cap, 1)), 64};
+    while (x.rg.hash_size < 2 * x.rg.cap) x.rg.hash_size *= 2;
+    return true;
+}
+
+static int run_region(int r, const EmulRegion& x, EmulSlot& ws, FILE* f)
+{
+    const AsmRegion& rg = x.rg;
+    std::vector<int32_t> rem(x.bases.size()), seg(x.bases.size());
+    for (const AsmSeq& s : x.seqs) segments(s, x.bases.data(), x.quals.data(), rem.data(), seg.data());
+    const AsmSlot w = ws.slot();
+    const int64_t pool_cap = std::min<int64_t>(rg.cap, HC_ASM_MAX_GRAPH_EDGES);
+    std::vector<hc_asm_edge> pool(static_cast<size_t>(pool_cap));
+    AsmOut o{};
+    unsigned long long used = 0;
+    int32_t err[2] = {0, 0};
+    AsmArgs a{};
+    a.regions = &rg;
+    a.n_regions = 1;
+    a.seqs = x.seqs.data();
+    a.n_seqs = int32_t(x.seqs.size());
+    a.bases = x.bases.data();
+    a.quals = x.quals.data();
+    a.rem = rem.data();
+    a.seg_start = seg.data();
+    a.out = &o;
+    a.edge_pool = pool.data();
+    a.edge_pool_cap = pool_cap;
+    a.edge_pool_used = &used;
+    a.err = err;
+    AsmShared sh{};
+    asm_region_graph(a, 0, w, &sh);
+    if (err[0]) {
+        std::fprintf(stderr, "region %d: device error word %d\n", r, err[0]);
+        return 4;
+    }
+    RegionResult rr;
+    std::memcpy(rr.attempts, o.attempts, sizeof(rr.attempts));
+    if (o.kmer_size) {
+        rr.kmer_size = o.kmer_size;
+        rr.source = o.source;
+        rr.sink = o.sink;
+        const hc_asm_edge* e = pool.data() + o.edge_off;
+        rr.edges.assign(e, e + o.n_edges);
+        paths_from_graph(x.bases.data() + o.source_pos, o.kmer_size, rr.edges.data(), o.n_edges, o.source, o.sink, rr);
+    }
+    print_region(f, rr);
+    return 0;
+}
+
+// one_slot: every region runs in the same slice, sized by the largest and never
+// cleared in between, as a workgroup of asm_graph_kernel that handles several
+// regions uses its slice. Otherwise every region gets exactly sized heap
+// blocks of its own, so that the sanitizer sees every overrun.
+static int mode_emul(const char* in, const char* outp, bool one_slot)
 {
     std::ifstream is(in);
     int n;
     is >> n;
+    std::vector<EmulRegion> regions(static_cast<size_t>(n));
+    for (EmulRegion& x : regions)
+        if (!read_region(is, x)) return 3;
     FILE* f = std::fopen(outp, "w");
-    for (int r = 0; r < n; ++r) {
-        std::string ref_hex;
-        int n_reads;
-        is >> ref_hex >> n_reads;
-        // exactly sized heap blocks, so that the sanitizer sees every overrun
-        std::vector<uint8_t> bases = unhex(ref_hex);
-        const int32_t ref_len = int32_t(bases.size());
-        std::vector<uint8_t> quals(bases.size(), 0);
-        std::vector<AsmSeq> seqs{AsmSeq{0, ref_len, 0, 1, 0}};
-        int64_t cap = std::max(0, ref_len - (kFirstK - 1));
-        for (int j = 0; j < n_reads; ++j) {
-            std::string bh, qh;
-            is >> bh >> qh;
-            const std::vector<uint8_t> b = unhex(bh), q = unhex(qh);
-            if (b.size() != q.size()) return 3;
-            seqs.push_back(AsmSeq{int64_t(bases.size()), int32_t(b.size()), int32_t(bases.size()), 0, 0});
-            bases.insert(bases.end(), b.begin(), b.end());
-            quals.insert(quals.end(), q.begin(), q.end());
-            cap += std::max<int64_t>(0, int64_t(b.size()) - (kFirstK - 1));
-        }
-        if (!is) return 3;
-        AsmRegion rg{0, ref_len, int32_t(bases.size()), int32_t(std::max<int64_t>(cap, 1)), 64};
-        while (rg.hash_size < 2 * rg.cap) rg.hash_size *= 2;
-        std::vector<int32_t> rem(bases.size()), seg(bases.size());
-        for (const AsmSeq& s : seqs) segments(s, bases.data(), quals.data(), rem.data(), seg.data());
-        std::vector<uint32_t> id(bases.size()), h_rep(size_t(rg.hash_size)), h_min(size_t(rg.hash_size));
-        std::vector<int32_t> vert_of(bases.size());
-        std::vector<uint8_t> dup(bases.size());
-        std::vector<AsmVertex> vs(size_t(rg.cap));
-        std::vector<AsmEdge> es(size_t(rg.cap));
-        const AsmSlot w{id.data(), vert_of.data(), dup.data(), h_rep.data(), h_min.data(), vs.data(), es.data()};
-        const int64_t pool_cap = std::min<int64_t>(rg.cap, HC_ASM_MAX_GRAPH_EDGES);
-        std::vector<hc_asm_edge> pool(static_cast<size_t>(pool_cap));
-        AsmOut o{};
-        unsigned long long used = 0;
-        int32_t err[2] = {0, 0};
-        AsmArgs a{};
-        a.regions = &rg;
-        a.n_regions = 1;
-        a.seqs = seqs.data();
-        a.n_seqs = int32_t(seqs.size());
-        a.bases = bases.data();
-        a.quals = quals.data();
-        a.rem = rem.data();
-        a.seg_start = seg.data();
-        a.out = &o;
-        a.edge_pool = pool.data();
-        a.edge_pool_cap = pool_cap;
-        a.edge_pool_used = &used;
-        a.err = err;
-        AsmShared sh{};
-        asm_region_graph(a, 0, w, &sh);
-        if (err[0]) {
-            std::fprintf(stderr, "region %d: device error word %d\n", r, err[0]);
-            return 4;
-        }
-        RegionResult rr;
-        std::memcpy(rr.attempts, o.attempts, sizeof(rr.attempts));
-        if (o.kmer_size) {
-            rr.kmer_size = o.kmer_size;
-            rr.source = o.source;
-            rr.sink = o.sink;
-            const hc_asm_edge* e = pool.data() + o.edge_off;
-            rr.edges.assign(e, e + o.n_edges);
-            paths_from_graph(bases.data() + o.source_pos, o.kmer_size, rr.edges.data(), o.n_edges, o.source, o.sink, rr);
-        }
-        print_region(f, rr);
+    EmulSlot shared;
+    if (one_slot)
+        for (const EmulRegion& x : regions) shared.grow(x.rg);
+    int rc = 0;
+    for (int r = 0; r < n && rc == 0; ++r) {
+        EmulSlot own;
+        if (!one_slot) own.grow(regions[size_t(r)].rg);
+        rc = run_region(r, regions[size_t(r)], one_slot ? shared : own, f);
     }
     std::fclose(f);
-    return 0;
+    return rc;
 }
 
 int main(int argc, char** argv)
@@ -266,7 +310,8 @@ int main(int argc, char** argv)
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "graph" && argc == 4) return mode_graph(argv[2], argv[3]);
     if (mode == "bubbles" && argc == 3) return mode_bubbles(std::atoi(argv[2]));
-    if (mode == "emul" && argc == 4) return mode_emul(argv[2], argv[3]);
-    std::fprintf(stderr, "usage: asm_host_main graph|emul <in> <out> | bubbles <n>\n");
+    if (mode == "emul" && argc == 4) return mode_emul(argv[2], argv[3], false);
+    if (mode == "emulslot" && argc == 4) return mode_emul(argv[2], argv[3], true);
+    std::fprintf(stderr, "usage: asm_host_main graph|emul|emulslot <in> <out> | bubbles <n>\n");
     return 1;
 }
